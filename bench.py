@@ -9,9 +9,15 @@
 A step = forward + nMSE loss + backward + (N>1: RCCL all-reduce of the flat gradient) + Adam on one batch that is
 already resident in HBM.  Workload = BASELINE.json configs[1]: Fno2d(in=2,out=2,p=5,L=4,hidden=20,modes=12), B=256 per
 GPU, 64x64, fp32.  Weak scaling: every rank processes its own B frames; value = N*B*K / max-over-ranks time.
-Rank 0 prints ONE JSON line.  Beside the contract's keys it carries
-  roofline                  dominant kernel of the step: ALGORITHMIC bytes per launch / HIP-event time vs 8 TB/s (SURVEY 8d)
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract's keys with `config`,
+`final_nmse` and
   roofline_step             the whole step against the ideal-fusion byte count of SURVEY 8d (10.2 MB/frame at C=20, L=4)
+  --dump-outputs DIR        after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32):
+                            preds, loss_sums (the tensor train_step returns), params / grads (the flat buffers after Adam, in
+                            abi_parameters order), adam_exp_avg / adam_exp_avg_sq.  At most 64 MB in all: an array over its share
+                            keeps a fixed, seeded sample of its leading-axis rows.  The inputs are seeded, so runs compare file by file.
+With --full (off by default) the line also carries
+  roofline                  dominant kernel of the step: ALGORITHMIC bytes per launch / HIP-event time vs 8 TB/s (SURVEY 8d)
   roofline_spectral_conv2d  the north-star kernel group (SpectralConv2d fwd+bwd, 5N + 3Wb bytes)
   kernels                   every kernel of the step: launches, average time, HBM fraction
   split2                    the same step and SpectralConv2d group with two-piece activation operands (cfd_tune_set("act_pieces", 2): rounds 1-4's default)
@@ -20,8 +26,9 @@ Rank 0 prints ONE JSON line.  Beside the contract's keys it carries
   train_66x65 / train_batch8 / train_c32_*  the same train step on the 66x65 grid (dam / tube / cylinder), at the reference's default batch 8 and default width 32
   unet_cfg2 / auto_deeponet_cfg3 / resnet_b32   train steps of BASELINE configs[2] / configs[3] and of the ResNet baseline on one GPU
   cpu_baseline              the reference's ATen call sequence on the host cores, at B = 256 and B = 32
+  dp                        (N > 1) the same K steps with the gradient exchange switched off: the exposed part of the all-reduces
 The rollout / rollout_66x65 legs run on EVERY rank (cases shard over the ranks, `n_gpus` inside the leg); the other extra legs
-run on rank 0 at N = 1 only.
+run on rank 0 at N = 1 only.  The --no-* options leave single legs out of a --full run.
 """
 from __future__ import annotations
 
@@ -72,6 +79,11 @@ def parse():
     ap.add_argument("--height", type=int, default=64)
     ap.add_argument("--width", type=int, default=64)
     ap.add_argument("--n-case-params", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the per-kernel roofline, rollout, extra-size / precision / route "
+                         "legs, the other model families, the CPU baseline and (N > 1) the exchange-off timing (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=10, help="timed steps of the cpu_baseline leg (SURVEY 8d: >= 10 after 3 warm-up steps)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -89,7 +101,12 @@ def parse():
                     help="no GPU: run ONLY the data-parallel skeleton of the step (rank launch, rendezvous, GradSync's per-phase "
                          "exchange of the model's flat gradient buffer, barrier / max-over-ranks timing, the JSON line) on host "
                          "tensors -- what tests/test_cpu_host.py drives; the line is marked dry_dp and is not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.only or args.dry_dp):
+        ap.error("--dump-outputs writes the headline step's outputs: not with --only or --dry-dp")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -658,6 +675,29 @@ def dry_dp(args, rank, world):
         sys.exit(4)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy as float32, smallest first, each within an equal share of what is left of
+    DUMP_BYTES.  An array over its share keeps a seeded sample of its leading-axis rows (of its elements where one row is already too
+    large), so the same shape always keeps the same rows."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = sorted(((k, t.detach().float().cpu().numpy()) for k, t in tensors.items()), key=lambda kv: kv[1].nbytes)
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            if a.ndim > 1 and a.nbytes // a.shape[0] > share:
+                a = a.reshape(-1)
+            k = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+        left -= a.nbytes
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -745,10 +785,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before anything below runs another step
+        dump_outputs(args.dump_outputs, dict(preds=eng.preds, loss_sums=eng.sums, params=eng.flat.data, grads=eng.gradients(),
+                                             adam_exp_avg=eng.exp_avg, adam_exp_avg_sq=eng.exp_avg_sq))
     final = eng.scores()
     fps = world * B * args.steps / elapsed
     dp_info = None
-    if eng.sync.exchange and not args.graph:
+    if args.full and eng.sync.exchange and not args.graph:
         # what the exchange costs this rank per step: the same K steps with the collectives switched off (same kernels: a data-parallel
         # engine keeps the step's five own launches), between the same barriers.  On N GPUs this is the exposed (un-hidden) part of the
         # all-reduces plus their host calls; it explains the scaling curve the driver computes from the per-N values.
@@ -792,13 +835,14 @@ def main():
 
     # ---- roofline leg: the same K steps again with per-kernel HIP events on the launch stream -------------------
     # EVERY rank runs these steps (they contain the gradient all-reduce, a collective); only rank 0 records events.
-    if not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if roofline:
         if rank == 0:
             api.call("cfd_prof_begin")
         for _ in range(args.steps):
             eng.train_step(inputs, label, cp, mask)
         torch.cuda.synchronize()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         rows = read_prof(api)
         tot_ms = sum(r[2] for r in rows)
         kern = []
@@ -825,7 +869,7 @@ def main():
             spectral_conv2d_bytes=sc.get("algorithmic_bytes"), spectral_conv2d_traffic=sc.get("traffic"),
             step_frac=result["roofline_step"]["frac"], step_bytes_per_frame=bpf, step_ms=result["ms_per_step"])
 
-    extra = rank == 0 and world == 1
+    extra = args.full and rank == 0 and world == 1
     # ---- rollout legs: batched multi-step inference from one HIP graph (the metric's "rollout" half; configs[4]) ----
     # Cases shard over the ranks with no collective on the data path (harness/test_multistep.py): EVERY rank rolls
     # out its own `--rollout-batch` cases, the legs are bracketed by barriers and timed by the slowest rank (weak scaling).
@@ -845,7 +889,7 @@ def main():
         res["cases_per_gpu"] = args.rollout_batch
         return res
 
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         ro = rollout_all_ranks(model, H, W)
         torch.manual_seed(0)
         m32 = Fno2d(2, 2, p, loss_name_to_fn("nmse"), 4, 12, 12, 32).to(dev)  # the reference's default width (args.py:190)

@@ -603,6 +603,36 @@ def test_bench_launcher_reports_a_failed_rank():
     assert "no CPU fallback" in r.stderr
 
 
+def test_bench_refuses_arguments_it_cannot_honour():
+    """No timed steps means no ms_per_step, and --dump-outputs belongs to the headline step only: both are refused up front."""
+    for flags in (("--steps", "0"), ("--dry-dp", "--dump-outputs", "x"), ("--only", "unet", "--dump-outputs", "x")):
+        r, lines = _run_bench(*flags, timeout=120)
+        assert r.returncode == 2 and not lines, flags
+
+
+def test_bench_dump_outputs_stays_within_its_budget_and_samples_the_same_rows(tmp_path, monkeypatch):
+    """bench.dump_outputs: every array lands as float32 .npy, the total stays within DUMP_BYTES, an oversized array keeps a seeded
+    sample of its rows (of its elements where one row is too large), and two dumps of the same tensors are identical."""
+    import sys
+    import torch
+    sys.path.insert(0, str(REPO))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    tensors = dict(small=torch.arange(4.0), whole=torch.arange(10000.0), rows=torch.randn(512, 2, 32, 32),
+                   one_row=torch.randn(1, 400000), f64=torch.ones(3, dtype=torch.float64))
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, tensors)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == set(tensors) and all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 1 << 20
+    assert np.array_equal(got["small"], [0, 1, 2, 3]) and np.array_equal(got["whole"], np.arange(10000.0)) and got["f64"].shape == (3,)
+    assert got["rows"].shape[1:] == (2, 32, 32) and 0 < got["rows"].shape[0] < 512 and got["one_row"].ndim == 1
+    rows = tensors["rows"].numpy()
+    assert all(any(np.array_equal(r, x) for x in rows) for r in got["rows"][:4])
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy")), k
+
+
 def test_ffn_routes_its_layers_to_the_stack_and_chain_kernels():
     """Host logic of models/ffn.py: which runs of Linear(+activation) layers go to the fused stack kernel (all widths <= 128), which to
     the Linear-chain node (wider runs of >= 2 layers), which stay single calls -- the partition the DeepONet variants rely on."""

@@ -688,3 +688,46 @@ def test_overlapping_copy_stream_hides_uploads_behind_kernels(torch):
         free[i & 1].record(cur)
     torch.cuda.synchronize()
     assert seen.tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+
+
+def test_bench_plain_run_dumps_what_its_last_timed_step_computed(torch, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: no extra legs): the line carries the contract's keys and no --full leg, and the
+    dumped arrays are those of the engine's step after settle + warm-up + K steps on bench.py's seeded model and batch, recomputed
+    here in-process."""
+    import os
+    import subprocess
+    import sys
+    from cfdbench_amd.engine import FnoTrainEngine
+    from cfdbench_amd.models.fno.fno2d import Fno2d
+    from cfdbench_amd.models.loss import loss_name_to_fn
+    repo = Path(__file__).resolve().parent.parent
+    B, steps, warmup, settle = 8, 3, 1, 2
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--settle", str(settle), "--batch", str(B), "--dump-outputs", str(tmp_path)],
+                       env=env, cwd=repo, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert not {"roofline", "kernels", "rollout", "cpu_baseline", "unet_cfg2", "split2"} & set(line)
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert set(got) == {"preds", "loss_sums", "params", "grads", "adam_exp_avg", "adam_exp_avg_sq"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20 and got["preds"].shape == (B, 2, 64, 64)
+
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = Fno2d(2, 2, 5, loss_name_to_fn("nmse"), 4, 12, 12, 20).to(dev)
+    eng = FnoTrainEngine(model, lr=1e-3, loss_name="nmse")
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    inputs = torch.randn(B, 2, 64, 64, generator=g).to(dev)
+    label = (inputs.cpu() + 0.1 * torch.randn(B, 2, 64, 64, generator=g)).to(dev)
+    cp = torch.randn(B, 5, generator=g).to(dev)
+    mask = torch.ones(B, 1, 64, 64, device=dev)
+    for _ in range(settle + warmup + steps):
+        eng.train_step(inputs, label, cp, mask)
+    want = dict(preds=eng.preds, loss_sums=eng.sums, params=eng.flat.data, grads=eng.gradients(), adam_exp_avg=eng.exp_avg,
+                adam_exp_avg_sq=eng.exp_avg_sq)
+    for k, t in want.items():
+        w = t.detach().cpu().numpy().astype(np.float64)
+        assert O.rel_nmse(got[k], w) < 1e-12, k

@@ -4,7 +4,7 @@
 TAG=${1:-r04z}
 cd $GRAFT_REPO_ROOT; OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log; tail -3 $OUT/pytest_gpu.log
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 bash tools/profile_step.sh $TAG/step > $OUT/profile_step.log 2>&1; tail -3 $OUT/profile_step.log
 bash tools/pmc_step.sh $TAG/busy > $OUT/pmc_step.log 2>&1; tail -3 $OUT/pmc_step.log
 for leg in spectral unet auto_deeponet; do
