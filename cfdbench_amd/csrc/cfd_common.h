@@ -135,6 +135,29 @@ int cfd_int_fno_head_fwd(const void* a, const float* mask, const float* label, c
                          const float* b2, float* preds, float* sums, void* ws, int B, int C, int Hd, int Co, int HW, int act_in,
                          int dt, void* stream);
 
+// Wide-channel route (wide.hip): layers with more than 32 input or output channels, up to CFD_WIDE_MAX, fp32 storage.
+#define CFD_WIDE_MAX 128
+int cfd_int_wide_mix(const cfd_plan* p, const float* xh, const float* w1, const float* w2, float* z, int B, int Cin, int Cout,
+                     int conj_t, void* stream);
+int cfd_int_wide_wgrad(const cfd_plan* p, const float* xh, const float* gh, float* gw1, float* gw2, int B, int Cin, int Cout,
+                       void* stream);
+int cfd_int_wide_chanmix(const float* in, const float* w, const float* bias, float* out, int B, int Ci, int Co, int HW, int act_in,
+                         int transpose, void* stream, const float* dgelu = nullptr);
+size_t cfd_int_wide_chan_wgrad_workspace_bytes(int B, int Ci, int Co, int HW);
+int cfd_int_wide_chan_wgrad(const float* g, const float* in, float* gw, float* gb, void* ws, int B, int Ci, int Co, int HW, int act_in,
+                            void* stream);
+int cfd_int_wide_stem_bwd(const cfd_plan* p, const float* g, const float* inputs, const float* mask, const float* case_params, float* gw,
+                          float* gb, void* ws, int B, int in_chan, int P, int C, void* stream);
+int cfd_int_wide_head_bwd(const float* a, const float* mask, const float* label, const float* preds, const float* gext, const float* coef,
+                          const float* w1, const float* b1, const float* w2, float* ga, float* gw1, float* gb1, float* gw2, float* gb2,
+                          void* ws, int B, int C, int Co, int HW, int act_in, void* stream);
+int cfd_int_wide_stem_fwd(const cfd_plan* p, const float* inputs, const float* mask, const float* case_params, const float* w,
+                          const float* bias, float* out, int B, int in_chan, int P, int C, void* stream);
+size_t cfd_int_wide_head_workspace_bytes(int B, int C, int Co, int HW);
+int cfd_int_wide_head_fwd(const float* a, const float* mask, const float* label, const float* w1, const float* b1, const float* w2,
+                          const float* b2, float* preds, float* sums, void* ws, int B, int C, int Co, int HW, int act_in, void* stream,
+                          int all_sums = 1);
+
 int cfd_int_fno_head_train(const void* a, const float* mask, const float* label, const float* coef, const float* w1, const float* b1,
                            const float* w2, const float* b2, float* preds, float* sums, float* ga, float* gw1, float* gb1,
                            float* gw2, float* gb2, void* ws, int B, int C, int Hd, int Co, int HW, int act_in, int dt, void* stream);

@@ -64,7 +64,8 @@ Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int 
     return L;
 }
 
-int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s) {
+// hidden 33 .. CFD_WIDE_MAX: the wide-channel route (wide.hip), fp32 activation storage only
+int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int dt = CFD_DT_F32) {
     CFD_REQUIRE(p && s, CFD_ERR_INVALID_ARG, "%s: NULL plan/shape", fn);
     CFD_REQUIRE(p->H == s->H && p->W == s->W && p->m1 == s->modes1 && p->m2 == s->modes2, CFD_ERR_INVALID_ARG,
                 "%s: plan is for %dx%d modes (%d,%d) but shape says %dx%d modes (%d,%d)", fn, p->H, p->W, p->m1, p->m2,
@@ -72,7 +73,9 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s) {
     CFD_REQUIRE(s->B >= 1, CFD_ERR_INVALID_ARG, "%s: empty batch", fn);
     CFD_REQUIRE(s->num_layers >= 0 && s->num_layers <= CFD_MAX_LAYERS, CFD_ERR_UNSUPPORTED, "%s: num_layers=%d (max %d)", fn,
                 s->num_layers, CFD_MAX_LAYERS);
-    CFD_REQUIRE(s->hidden >= 1 && s->hidden <= 32, CFD_ERR_UNSUPPORTED, "%s: hidden=%d (max 32)", fn, s->hidden);
+    CFD_REQUIRE(s->hidden >= 1 && s->hidden <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "%s: hidden=%d (max %d)", fn, s->hidden, CFD_WIDE_MAX);
+    CFD_REQUIRE(s->hidden <= 32 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: hidden=%d: bf16 activation storage needs hidden <= 32", fn,
+                s->hidden);
     return CFD_OK;
 }
 
@@ -84,6 +87,8 @@ Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, ch
                   const void* mask) {
     const int B = s->B, C = s->hidden, NL = s->num_layers;
     Deferred d{};
+    // the wide route (hidden > 32) has none of the fused kernels that carry a deferred job: every flag is ignored there
+    if (C > 32) return d;
     d.scale = (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     const float* gA = (const float*)(base + L.off_gA);
     const float* gB = (const float*)(base + L.off_gB);
@@ -120,7 +125,7 @@ extern "C" int cfd_fno_forward(const cfd_plan* p, const cfd_fno_shape* s, const 
 extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, const cfd_fno_params* prm, const float* inputs,
                                   const float* case_params, const float* mask, const float* label, float* preds,
                                   float* sums, void* ws, int training, int act_dtype, void* stream) {
-    CFD_TRY(check_shape("cfd_fno_forward", p, s));
+    CFD_TRY(check_shape("cfd_fno_forward", p, s, act_dtype));
     CFD_REQUIRE(prm && inputs && preds && ws, CFD_ERR_INVALID_ARG, "cfd_fno_forward: NULL pointer");
     CFD_REQUIRE(!label || sums, CFD_ERR_INVALID_ARG, "cfd_fno_forward: label given without sums");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_forward: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
@@ -189,7 +194,7 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
                                        const cfd_fno_params* g, const float* inputs, const float* case_params,
                                        const float* mask, const float* label, float* preds, float* sums, float* coef, void* ws,
                                        int which, float upstream, int act_dtype, int flags, void* stream) {
-    CFD_TRY(check_shape("cfd_fno_forward_train", p, s));
+    CFD_TRY(check_shape("cfd_fno_forward_train", p, s, act_dtype));
     CFD_REQUIRE(which >= 0 && which <= 2, CFD_ERR_INVALID_ARG, "cfd_fno_forward_train: which must be 0 (mse), 1 (nmse), 2 (mae)");
     CFD_REQUIRE(prm && g && inputs && label && preds && sums && ws && (coef || ((flags & CFD_TRAIN_DEFER_SCALE) && which == 1)), CFD_ERR_INVALID_ARG,
                 "cfd_fno_forward_train: NULL pointer");
@@ -232,6 +237,12 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
     }
     CFD_TRY(cfd_side_join((hipStream_t)stream, side));
     // deferred normaliser: the mse coefficient by value, sum (label*mask)^2 and the count leave the head's reduction (sums[2], sums[3])
+    if (C > 32) {  // wide route: head forward (sums[0..1]; sums[2..3] and coef came from cfd_label_energy_coef), then its backward
+        CFD_TRY(cfd_int_wide_head_fwd((const float*)act_buf(NL), mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
+                                      scratch, B, C, s->out_chan, HW, NL > 0, stream, 0));
+        return cfd_int_wide_head_bwd((const float*)act_buf(NL), mask, label, preds, nullptr, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, gA,
+                                     g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->out_chan, HW, NL > 0, stream);
+    }
     const float count = (float)((double)B * s->out_chan * HW);
     HeadTail ht{};
     return cfd_int_fno_head_train_f(act_buf(NL), mask, label, df.scale ? nullptr : coef, upstream / count, 0.f, df.scale ? count : 0.f,
@@ -266,7 +277,7 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
                                         const float* mask, const float* label, const float* preds,
                                         const float* gpreds_ext, const float* coef, float* sums, void* ws, int phase, int which,
                                         int act_dtype, int flags, void* stream) {
-    CFD_TRY(check_shape("cfd_fno_backward_phase", p, s));
+    CFD_TRY(check_shape("cfd_fno_backward_phase", p, s, act_dtype));
     CFD_REQUIRE(prm && g && inputs && ws, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     const int dt = act_dtype;
@@ -359,7 +370,7 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
                                  float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                                  float beta2, float eps, float weight_decay, int step, float grad_scale, int which, int act_dtype,
                                  int flags, void* stream) {
-    CFD_TRY(check_shape("cfd_fno_adam_step", p, s));
+    CFD_TRY(check_shape("cfd_fno_adam_step", p, s, act_dtype));
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
     const Layout L = make_layout(p, s, 1, act_dtype);

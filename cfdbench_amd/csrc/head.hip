@@ -333,7 +333,9 @@ extern "C" size_t cfd_fno_head_workspace_bytes(int B, int C, int Hd, int Co, int
     if (B <= 0) return 0;
     const size_t fwd = (size_t)head_blocks(B, HW, false, 0) * 3 * sizeof(float);
     const size_t bwd = (size_t)head_bwd_blocks(B, HW, false) * head_part_floats(C, Co) * sizeof(float);
-    return fwd > bwd ? fwd : bwd;
+    const size_t r = fwd > bwd ? fwd : bwd;
+    const size_t wide = C > 32 ? cfd_int_wide_head_workspace_bytes(B, C, Co, HW) : 0;
+    return r > wide ? r : wide;
 }
 
 static int head_check(const char* fn, int B, int C, int Hd, int Co, int HW) {
@@ -358,6 +360,12 @@ int cfd_int_fno_head_fwd(const void* a_, const float* mask, const float* label, 
     const float* a = (const float*)a_;
     CFD_REQUIRE(a && w1 && b1 && w2 && b2 && preds, CFD_ERR_INVALID_ARG, "cfd_fno_head_fwd: NULL pointer");
     CFD_REQUIRE(!label || (sums && ws), CFD_ERR_INVALID_ARG, "cfd_fno_head_fwd: label given without sums/workspace");
+    if (C > 32 && C <= CFD_WIDE_MAX) {  // wide channels (wide.hip): the same checks at the wider bound
+        CFD_TRY(head_check("cfd_fno_head_fwd", B, 32, Hd, Co, HW));
+        CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_head_fwd: bf16 activation storage needs hidden <= 32 (hidden=%d)", C);
+        if (B == 0) return CFD_OK;
+        return cfd_int_wide_head_fwd(a, mask, label, w1, b1, w2, b2, preds, sums, ws, B, C, Co, HW, act_in, stream);
+    }
     CFD_TRY(head_check("cfd_fno_head_fwd", B, C, Hd, Co, HW));
     if (B == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1012,6 +1020,11 @@ extern "C" int cfd_fno_head_bwd(const float* a, const float* mask, const float* 
     CFD_REQUIRE(a && w1 && b1 && w2 && ga && gw1 && gb1 && gw2 && gb2 && ws, CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: NULL pointer");
     CFD_REQUIRE(!label || (preds && coef), CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: label given without preds/coef");
     CFD_REQUIRE(label || gpreds_ext, CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: neither a loss (label) nor an upstream gradient given");
+    if (C > 32 && C <= CFD_WIDE_MAX) {  // wide channels (wide.hip)
+        CFD_TRY(head_check("cfd_fno_head_bwd", B, 32, Hd, Co, HW));
+        CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: empty batch");
+        return cfd_int_wide_head_bwd(a, mask, label, preds, gpreds_ext, coef, w1, b1, w2, ga, gw1, gb1, gw2, gb2, ws, B, C, Co, HW, act_in, stream);
+    }
     CFD_TRY(head_check("cfd_fno_head_bwd", B, C, Hd, Co, HW));
     CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: empty batch");
     hipStream_t st = (hipStream_t)stream;
@@ -1064,6 +1077,14 @@ int cfd_int_fno_head_train(const void* a, const float* mask, const float* label,
                            const float* w2, const float* b2, float* preds, float* sums, float* ga, float* gw1, float* gb1,
                            float* gw2, float* gb2, void* ws, int B, int C, int Hd, int Co, int HW, int act_in, int dt, void* stream) {
     CFD_REQUIRE(coef, CFD_ERR_INVALID_ARG, "cfd_fno_head_train: NULL pointer");
+    if (C > 32 && C <= CFD_WIDE_MAX) {  // wide channels (wide.hip): forward (sums[0..1]) and backward as two passes
+        CFD_TRY(head_check("cfd_fno_head_train", B, 32, Hd, Co, HW));
+        CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_head_train: bf16 activation storage needs hidden <= 32 (hidden=%d)", C);
+        CFD_REQUIRE(a && label && preds && sums && ga && ws, CFD_ERR_INVALID_ARG, "cfd_fno_head_train: NULL pointer");
+        CFD_TRY(cfd_int_wide_head_fwd((const float*)a, mask, label, w1, b1, w2, b2, preds, sums, ws, B, C, Co, HW, act_in, stream, 0));
+        return cfd_int_wide_head_bwd((const float*)a, mask, label, preds, nullptr, coef, w1, b1, w2, ga, gw1, gb1, gw2, gb2, ws, B, C, Co, HW,
+                                     act_in, stream);
+    }
     return cfd_int_fno_head_train_f(a, mask, label, coef, 0.f, 0.f, 0.f, w1, b1, w2, b2, preds, sums, ga, gw1, gb1, gw2, gb2, ws, B, C, Hd, Co, HW,
                                     act_in, dt, stream, nullptr);
 }

@@ -207,9 +207,11 @@ int cfd_int_fno_stem_fwd(const cfd_plan* p, const float* inputs, const float* ma
     float* out = (float*)out_;
     CFD_REQUIRE(p && inputs && w && bias && out && (P == 0 || case_params), CFD_ERR_INVALID_ARG, "cfd_fno_stem_fwd: NULL pointer");
     CFD_REQUIRE(B >= 0 && in_chan >= 1 && P >= 0 && C >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_stem_fwd: bad sizes");
-    CFD_REQUIRE(in_chan + 3 + P <= 32 && C <= 32, CFD_ERR_UNSUPPORTED,
-                "cfd_fno_stem_fwd: features=%d (max 32) / hidden=%d (max 32) unsupported", in_chan + 3 + P, C);
+    CFD_REQUIRE(in_chan + 3 + P <= 32 && C <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED,
+                "cfd_fno_stem_fwd: features=%d (max 32) / hidden=%d (max %d) unsupported", in_chan + 3 + P, C, CFD_WIDE_MAX);
+    CFD_REQUIRE(C <= 32 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_stem_fwd: bf16 activation storage needs hidden <= 32 (hidden=%d)", C);
     if (B == 0) return CFD_OK;
+    if (C > 32) return cfd_int_wide_stem_fwd(p, inputs, mask, case_params, w, bias, out, B, in_chan, P, C, stream);  // wide.hip
     const long total = (long)B * p->H * p->W;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
@@ -577,8 +579,10 @@ extern "C" int cfd_chanmix(const float* in, const float* w, const float* bias, f
                            int act_in, int transpose, void* stream) {
     CFD_REQUIRE(in && w && out, CFD_ERR_INVALID_ARG, "cfd_chanmix: NULL pointer");
     CFD_REQUIRE(B >= 0 && Ci >= 1 && Co >= 1 && HW >= 1, CFD_ERR_INVALID_ARG, "cfd_chanmix: bad sizes");
-    CFD_REQUIRE(Ci <= 32 && Co <= 32, CFD_ERR_UNSUPPORTED, "cfd_chanmix: Ci=%d Co=%d (max 32) unsupported", Ci, Co);
+    CFD_REQUIRE(Ci <= CFD_WIDE_MAX && Co <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_chanmix: Ci=%d Co=%d (max %d) unsupported", Ci, Co,
+                CFD_WIDE_MAX);
     if (B == 0) return CFD_OK;
+    if (Ci > 32 || Co > 32) return cfd_int_wide_chanmix(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, stream);  // wide.hip
     hipStream_t st = (hipStream_t)stream;
     if (cfd_tune_get(CFD_TUNE_EXACT_FP32) != 1)  // split-bf16 MFMA form; the VALU kernel below is the exact-fp32 route
         return launch_chanmix_b3<float>(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, st);
@@ -851,6 +855,7 @@ static int wgrad_blocks(int B, int HW) {
 
 extern "C" size_t cfd_chan_wgrad_workspace_bytes(int B, int Ci, int Co, int HW) {
     if (B <= 0) return 0;
+    if (Ci > 32 || Co > 32) return cfd_int_wide_chan_wgrad_workspace_bytes(B, Ci, Co, HW);  // wide.hip
     return (size_t)wgrad_blocks(B, HW) * Co * (Ci + 1) * sizeof(float);
 }
 
@@ -917,7 +922,9 @@ extern "C" int cfd_chan_wgrad(const float* g, const float* in, float* gw, float*
                               int HW, int act_in, void* stream) {
     CFD_REQUIRE(g && in && gw && ws, CFD_ERR_INVALID_ARG, "cfd_chan_wgrad: NULL pointer");
     CFD_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && HW >= 1, CFD_ERR_INVALID_ARG, "cfd_chan_wgrad: bad sizes");
-    CFD_REQUIRE(Ci <= 32 && Co <= 32, CFD_ERR_UNSUPPORTED, "cfd_chan_wgrad: Ci=%d Co=%d (max 32) unsupported", Ci, Co);
+    CFD_REQUIRE(Ci <= CFD_WIDE_MAX && Co <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_chan_wgrad: Ci=%d Co=%d (max %d) unsupported", Ci, Co,
+                CFD_WIDE_MAX);
+    if (Ci > 32 || Co > 32) return cfd_int_wide_chan_wgrad(g, in, gw, gb, ws, B, Ci, Co, HW, act_in, stream);  // wide.hip
     StemSrc ss{};
     return launch_wgrad<false>(g, in, ss, gw, gb, ws, B, Ci, Co, HW, act_in, (hipStream_t)stream);
 }
@@ -933,7 +940,12 @@ int cfd_int_chan_wgrad_dt(const float* g, const void* in, float* gw, float* gb, 
     if (defer) defer->part = nullptr;
     CFD_REQUIRE(g && in && gw && ws, CFD_ERR_INVALID_ARG, "cfd_chan_wgrad: NULL pointer");
     CFD_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && HW >= 1, CFD_ERR_INVALID_ARG, "cfd_chan_wgrad: bad sizes");
-    CFD_REQUIRE(Ci <= 32 && Co <= 32, CFD_ERR_UNSUPPORTED, "cfd_chan_wgrad: Ci=%d Co=%d (max 32) unsupported", Ci, Co);
+    CFD_REQUIRE(Ci <= CFD_WIDE_MAX && Co <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_chan_wgrad: Ci=%d Co=%d (max %d) unsupported", Ci, Co,
+                CFD_WIDE_MAX);
+    if (Ci > 32 || Co > 32) {  // wide.hip (fp32 storage only; its reduction is launched here, nothing is deferred)
+        CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_chan_wgrad: bf16 activation storage needs Ci, Co <= 32 (Ci=%d Co=%d)", Ci, Co);
+        return cfd_int_wide_chan_wgrad(g, (const float*)in, gw, gb, ws, B, Ci, Co, HW, act_in, stream);
+    }
     StemSrc ss{};
     if (dt == CFD_DT_BF16)
         return launch_wgrad<false, __bf16>(g, (const __bf16*)in, ss, gw, gb, ws, B, Ci, Co, HW, act_in, (hipStream_t)stream, defer);
@@ -949,7 +961,8 @@ extern "C" int cfd_fno_stem_bwd(const cfd_plan* p, const float* g, const float* 
                                 const float* case_params, float* gw, float* gb, void* ws, int B, int in_chan, int P,
                                 int C, void* stream) {
     CFD_REQUIRE(p && g && inputs && gw && gb && ws && (P == 0 || case_params), CFD_ERR_INVALID_ARG, "cfd_fno_stem_bwd: NULL pointer");
-    CFD_REQUIRE(in_chan + 3 + P <= 32 && C <= 32, CFD_ERR_UNSUPPORTED, "cfd_fno_stem_bwd: too many features/channels");
+    CFD_REQUIRE(in_chan + 3 + P <= 32 && C <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_fno_stem_bwd: too many features/channels");
+    if (C > 32) return cfd_int_wide_stem_bwd(p, g, inputs, mask, case_params, gw, gb, ws, B, in_chan, P, C, stream);  // wide.hip
     StemSrc ss{mask, case_params, p->d_gx, p->d_gy, in_chan, P, p->W};
     return launch_wgrad<true>(g, inputs, ss, gw, gb, ws, B, in_chan + 3 + P, C, p->H * p->W, 0, (hipStream_t)stream);
 }

@@ -1032,8 +1032,10 @@ extern "C" int cfd_spectral_mix(const cfd_plan* p, const float* xh, const float*
                                 int Cin, int Cout, int conj_t, void* stream) {
     CFD_REQUIRE(p && xh && w1 && w2 && z, CFD_ERR_INVALID_ARG, "cfd_spectral_mix: NULL pointer");
     CFD_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1, CFD_ERR_INVALID_ARG, "cfd_spectral_mix: bad sizes");
-    CFD_REQUIRE(Cin <= 32 && Cout <= 32, CFD_ERR_UNSUPPORTED, "cfd_spectral_mix: Cin=%d Cout=%d (max 32) unsupported", Cin, Cout);
+    CFD_REQUIRE(Cin <= CFD_WIDE_MAX && Cout <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_spectral_mix: Cin=%d Cout=%d (max %d) unsupported", Cin,
+                Cout, CFD_WIDE_MAX);
     if (B == 0) return CFD_OK;
+    if (Cin > 32 || Cout > 32) return cfd_int_wide_mix(p, xh, w1, w2, z, B, Cin, Cout, conj_t, stream);  // wide.hip
     const int Cr = conj_t ? Cout : Cin, Cz = conj_t ? Cin : Cout;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(conj_t ? "k_mix_adj" : "k_mix", st, 16.0 * p->m1 * p->m2 * ((double)B * (Cin + Cout) + (double)Cin * Cout),
@@ -1321,6 +1323,7 @@ __global__ __launch_bounds__(256) void k_spec_wgrad_reduce(const float2* __restr
 
 extern "C" size_t cfd_spectral_wgrad_workspace_bytes(const cfd_plan* p, int B, int Cin, int Cout) {
     if (!p || B <= 0) return 0;
+    if (Cin > 32 || Cout > 32) return 0;  // the wide route (wide.hip) sums the batch in place: no partial records
     size_t nchunk = (B + CFD_WGRAD_BCHUNK - 1) / CFD_WGRAD_BCHUNK;
     int nmg, npair, BC, nct;
     cfd_wgrad_tile_geometry(B, 2 * p->m1 * p->m2, &nmg, &npair, &BC, &nct);
@@ -1351,9 +1354,11 @@ static bool launch_spec_wgrad_tile(const float2* xh, const float2* gh, float2* p
 
 extern "C" int cfd_spectral_wgrad(const cfd_plan* p, const float* xh, const float* gh, float* gw1, float* gw2, void* ws,
                                   int B, int Cin, int Cout, void* stream) {
-    CFD_REQUIRE(p && xh && gh && gw1 && gw2 && ws, CFD_ERR_INVALID_ARG, "cfd_spectral_wgrad: NULL pointer");
+    CFD_REQUIRE(p && xh && gh && gw1 && gw2 && (ws || Cin > 32 || Cout > 32), CFD_ERR_INVALID_ARG, "cfd_spectral_wgrad: NULL pointer");
     CFD_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1, CFD_ERR_INVALID_ARG, "cfd_spectral_wgrad: bad sizes");
-    CFD_REQUIRE(Cin <= 32 && Cout <= 32, CFD_ERR_UNSUPPORTED, "cfd_spectral_wgrad: Cin=%d Cout=%d (max 32) unsupported", Cin, Cout);
+    CFD_REQUIRE(Cin <= CFD_WIDE_MAX && Cout <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "cfd_spectral_wgrad: Cin=%d Cout=%d (max %d) unsupported", Cin,
+                Cout, CFD_WIDE_MAX);
+    if (Cin > 32 || Cout > 32) return cfd_int_wide_wgrad(p, xh, gh, gw1, gw2, B, Cin, Cout, stream);  // wide.hip (no partial sums)
     const int M = 2 * p->m1 * p->m2;
     int nchunk = (B + CFD_WGRAD_BCHUNK - 1) / CFD_WGRAD_BCHUNK;
     const long total = (long)Cin * Cout * M;
@@ -1404,7 +1409,8 @@ int cfd_int_spectral_mix_adj_wgrad(const cfd_plan* p, const float* xh, const flo
                               float* gz, float* gw1, float* gw2, void* ws, int B, int Cin, int Cout, void* stream,
                               SpecWgradTail* defer) {
     if (defer) defer->part = nullptr;
-    CFD_REQUIRE(p && xh && gh && w1 && w2 && gz && gw1 && gw2 && ws, CFD_ERR_INVALID_ARG, "cfd_spectral_mix_adj_wgrad: NULL pointer");
+    CFD_REQUIRE(p && xh && gh && w1 && w2 && gz && gw1 && gw2 && (ws || Cin > 32 || Cout > 32), CFD_ERR_INVALID_ARG,
+                "cfd_spectral_mix_adj_wgrad: NULL pointer");
     CFD_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1, CFD_ERR_INVALID_ARG, "cfd_spectral_mix_adj_wgrad: bad sizes");
     if (cfd_fused_disabled() || Cin != Cout || (Cin != 20 && Cin != 32)) {
         CFD_TRY(cfd_spectral_wgrad(p, xh, gh, gw1, gw2, ws, B, Cin, Cout, stream));
@@ -2582,11 +2588,12 @@ static bool launch_block(const cfd_plan* p, const float* src, const float* z, co
 extern "C" int cfd_fno_block_fwd(const cfd_plan* p, const float* a, const float* z, const float* w0, const float* b0,
                                  float* out, int B, int Cin, int Cout, int act_in, void* stream) {
     CFD_REQUIRE(p && a && z && w0 && out, CFD_ERR_INVALID_ARG, "cfd_fno_block_fwd: NULL pointer");
-    CFD_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1 && Cin <= 32 && Cout <= 32, CFD_ERR_UNSUPPORTED,
-                "cfd_fno_block_fwd: channels (%d -> %d) unsupported (1..32)", Cin, Cout);
+    CFD_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1 && Cin <= CFD_WIDE_MAX && Cout <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED,
+                "cfd_fno_block_fwd: channels (%d -> %d) unsupported (1..%d)", Cin, Cout, CFD_WIDE_MAX);
     if (B == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (!block_fused_ok(p, Cin, Cout, a, out, nullptr, z, B, false)) {  // general grids: two passes
+    const bool wide = Cin > 32 || Cout > 32;
+    if (wide || !block_fused_ok(p, Cin, Cout, a, out, nullptr, z, B, false)) {  // general grids and wide channels: two passes
         CFD_TRY(cfd_chanmix(a, w0, b0, out, B, Cin, Cout, p->H * p->W, act_in, 0, stream));
         return cfd_spectral_idft(p, z, out, nullptr, out, B * Cout, 1, stream);
     }
@@ -2627,7 +2634,7 @@ static int launch_reduce_tail_standalone(const CfdReduceTail* tail, hipStream_t 
 
 // whether cfd_int_fno_block_bwd_input will run the fused kernel (the one that carries tail jobs) for this plan / width / buffers
 bool cfd_int_block_bwd_fused(const cfd_plan* p, int B, int C, const void* g, const void* gin, const void* aprev, const void* gz) {
-    return block_fused_ok(p, C, C, g, gin, aprev, gz, B, true);
+    return C <= 32 && block_fused_ok(p, C, C, g, gin, aprev, gz, B, true);
 }
 
 // ---- lifting-layer gradient from the sums of k_block<.., STEMG> (cfd_tail.h: CfdStemG) ------------------------------------------
@@ -2672,11 +2679,12 @@ int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp,
 int cfd_int_fno_block_bwd_input(const cfd_plan* p, const float* g, const float* gz, const float* w0, const float* aprev,
                                 float* gin, int B, int Cin, int Cout, void* stream, const CfdReduceTail* tail, const CfdStemG* stemg) {
     CFD_REQUIRE(p && g && gz && w0 && gin, CFD_ERR_INVALID_ARG, "cfd_fno_block_bwd_input: NULL pointer");
-    CFD_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1 && Cin <= 32 && Cout <= 32, CFD_ERR_UNSUPPORTED,
-                "cfd_fno_block_bwd_input: channels (%d -> %d) unsupported (1..32)", Cin, Cout);
+    CFD_REQUIRE(B >= 0 && Cin >= 1 && Cout >= 1 && Cin <= CFD_WIDE_MAX && Cout <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED,
+                "cfd_fno_block_bwd_input: channels (%d -> %d) unsupported (1..%d)", Cin, Cout, CFD_WIDE_MAX);
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) return launch_reduce_tail_standalone(tail, st);
-    if (!block_fused_ok(p, Cout, Cin, g, gin, aprev, gz, B, true)) {
+    const bool wide = Cin > 32 || Cout > 32;
+    if (wide || !block_fused_ok(p, Cout, Cin, g, gin, aprev, gz, B, true)) {  // general grids and wide channels: two passes
         CFD_REQUIRE(!(stemg && stemg->inputs), CFD_ERR_UNSUPPORTED, "cfd_fno_block_bwd_input: the lifting-layer sums need the fused kernel (cfd_int_stemg_ok)");
         CFD_TRY(launch_reduce_tail_standalone(tail, st));
         CFD_TRY(cfd_chanmix(g, w0, nullptr, gin, B, Cout, Cin, p->H * p->W, 0, 1, stream));

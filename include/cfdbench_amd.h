@@ -125,7 +125,7 @@ int cfd_fno_block_bwd_input(const cfd_plan* plan, const float* g, const float* g
 
 /* out[b,o,p] = bias[o] + sum_i w[o,i] f(in[b,i,p])   (nn.Conv2d(k=1): fno2d.py:104,150; transpose=1 uses w[i,o]
  * and is the input-gradient of the same conv).  in: (B,Ci,HW); out: (B,Co,HW); w: (Co,Ci) (or (Ci,Co) rows if
- * transpose); bias may be NULL.  act_in as in cfd_spectral_dft.  Ci,Co <= 32.                              */
+ * transpose); bias may be NULL.  act_in as in cfd_spectral_dft.  Ci,Co <= 128 (> 32: the wide route, wide.hip). */
 int cfd_chanmix(const float* in, const float* w, const float* bias, float* out, int B, int Ci, int Co, int HW,
                 int act_in, int transpose, void* stream);
 
