@@ -84,7 +84,34 @@ struct cfd_plan {
     float* d_clhw;  // [m2]  c_l / (H*W)
     float* d_gx;    // [H]  np.linspace(0,1,H) as float32   (fno2d.py:251)
     float* d_gy;    // [W]
+    // Many-modes route (dft_many.hip): every plan with m1 > 15 or m2 > 16.  Such a plan has only the fp32 tables below (d_fwd, d_inv,
+    // d_fwd_b3, d_inv_b3, d_fwd_g, d_inv_g, d_tail are NULL), the narrow plans have NULL here.  Dimensions: cfd_many_dims().
+    int many;
+    float* d_many_fwd;  // T1[Wk][N1p] (column c < m2: cos, m2 <= c < 2 m2: -sin of 2 pi l y / W) | T2C[R2p][Hk] | T2S[R2p][Hk] (cos / sin of
+                        // 2 pi K[r] x / H for kept row r); zero outside y < W, c < 2 m2, r < 2 m1, x < H
+    float* d_many_inv;  // TB[K2][Wq] (c < m2: c_l/HW cos, m2 <= c < 2 m2: -c_l/HW sin) | TAC[Hp][R4] | TAS[Hp][R4] (cos / sin of 2 pi K[r] x / H)
 };
+
+// Padded extents of the many-modes tables and kernels: H, W rounded up to 4 (k-steps of v_mfma_f32_16x16x4_f32) and 16 (output tiles),
+// 2 m2 rounded up to 16 (forward stage-1 columns) and 4 (inverse stage-B k-steps), 2 m1 rounded up to 16 (forward stage-2 rows) and 4
+// (inverse stage-A k-steps).
+struct CfdManyDims {
+    int Hk, Hp, Wk, Wq, N1p, K2, R2p, R4;
+};
+__host__ __device__ static inline CfdManyDims cfd_many_dims(int H, int W, int m1, int m2) {
+    CfdManyDims d;
+    d.Hk = (H + 3) / 4 * 4;
+    d.Hp = (H + 15) / 16 * 16;
+    d.Wk = (W + 3) / 4 * 4;
+    d.Wq = (W + 15) / 16 * 16;
+    d.N1p = (2 * m2 + 15) / 16 * 16;
+    d.K2 = (2 * m2 + 3) / 4 * 4;
+    d.R2p = (2 * m1 + 15) / 16 * 16;
+    d.R4 = (2 * m1 + 3) / 4 * 4;
+    return d;
+}
+int cfd_int_dft_many(const cfd_plan* p, const float* x, float* xh, int nimg, int act_in, void* stream);
+int cfd_int_idft_many(const cfd_plan* p, const float* z, const float* addend, const float* aprev, float* out, int nimg, int epi, void* stream);
 
 static inline size_t cfd_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

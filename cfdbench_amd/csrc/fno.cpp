@@ -64,7 +64,7 @@ Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int 
     return L;
 }
 
-// hidden 33 .. CFD_WIDE_MAX: the wide-channel route (wide.hip), fp32 activation storage only
+// hidden 33 .. CFD_WIDE_MAX: the wide-channel route (wide.hip), fp32 activation storage only; the same for many-modes plans (dft_many.hip)
 int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int dt = CFD_DT_F32) {
     CFD_REQUIRE(p && s, CFD_ERR_INVALID_ARG, "%s: NULL plan/shape", fn);
     CFD_REQUIRE(p->H == s->H && p->W == s->W && p->m1 == s->modes1 && p->m2 == s->modes2, CFD_ERR_INVALID_ARG,
@@ -76,6 +76,8 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     CFD_REQUIRE(s->hidden >= 1 && s->hidden <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "%s: hidden=%d (max %d)", fn, s->hidden, CFD_WIDE_MAX);
     CFD_REQUIRE(s->hidden <= 32 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: hidden=%d: bf16 activation storage needs hidden <= 32", fn,
                 s->hidden);
+    CFD_REQUIRE(!p->many || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED,
+                "%s: modes (%d,%d): bf16 activation storage needs modes1 <= 15 and modes2 <= 16", fn, p->m1, p->m2);
     return CFD_OK;
 }
 
@@ -87,8 +89,9 @@ Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, ch
                   const void* mask) {
     const int B = s->B, C = s->hidden, NL = s->num_layers;
     Deferred d{};
-    // the wide route (hidden > 32) has none of the fused kernels that carry a deferred job: every flag is ignored there
-    if (C > 32) return d;
+    // the wide route (hidden > 32) and the many-modes route have none of the fused kernels that carry a deferred job: every flag is
+    // ignored there
+    if (C > 32 || p->many) return d;
     d.scale = (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     const float* gA = (const float*)(base + L.off_gA);
     const float* gB = (const float*)(base + L.off_gB);

@@ -41,14 +41,93 @@ static int upload(const std::vector<float>& h, float** d) {
     return CFD_OK;
 }
 
+// coordinate grids: np.linspace(0, 1, n) in float64, cast to float32 (fno2d.py:251,253)
+static void make_grids(int H, int W, std::vector<float>& gx, std::vector<float>& gy) {
+    gx.resize(H);
+    gy.resize(W);
+    for (int i = 0; i < H; ++i) gx[i] = (i == H - 1) ? 1.0f : (float)((double)i * (1.0 / (double)(H - 1)));
+    for (int i = 0; i < W; ++i) gy[i] = (i == W - 1) ? 1.0f : (float)((double)i * (1.0 / (double)(W - 1)));
+}
+
+// c_l / (H W) of the C2R transform: c_0 = 1 and, for even W, c = 1 at the Nyquist column l = W/2; 2 otherwise
+static double hermitian_scale(int l, int H, int W) {
+    return ((l == 0 || (W % 2 == 0 && l == W / 2)) ? 1.0 : 2.0) / ((double)H * W);
+}
+
+// The many-modes plan (m1 > 15 or m2 > 16): fp32 tables of the two GEMM stages of dft_many.hip, built in double precision, zero-padded
+// to the extents of cfd_many_dims() so that the kernels read whole 16 x 4 / 4 x 16 operand fragments without bounds checks.
+static int cfd_plan_create_many(int H, int W, int m1, int m2, cfd_plan** out) {
+    cfd_plan* p = new cfd_plan();
+    p->H = H; p->W = W; p->m1 = m1; p->m2 = m2;
+    p->many = 1;
+    p->NJ = (W + 15) / 16;
+    if (p->NJ < 4) p->NJ = 4;
+    p->KX = (H / 2 + 1 + 3) / 4;
+    p->T = (H + 15) / 16;
+    p->NJG = (W + 15) / 16;
+    p->NHG = (p->NJG + 1) / 2;
+    const CfdManyDims d = cfd_many_dims(H, W, m1, m2);
+    const double PI2 = 6.283185307179586476925286766559;
+    auto krow = [&](int r) { return r < m1 ? r : H - 2 * m1 + r; };  // kept row r -> frequency K[r]: [0, m1) U [H - m1, H)
+    std::vector<float> fwd((size_t)d.Wk * d.N1p + 2 * (size_t)d.R2p * d.Hk, 0.f);
+    float* t1 = fwd.data();
+    float* t2c = t1 + (size_t)d.Wk * d.N1p;
+    float* t2s = t2c + (size_t)d.R2p * d.Hk;
+    for (int y = 0; y < W; ++y)
+        for (int l = 0; l < m2; ++l) {
+            const double ph = PI2 * (double)((long)l * y % W) / W;
+            t1[(size_t)y * d.N1p + l] = (float)std::cos(ph);
+            t1[(size_t)y * d.N1p + m2 + l] = (float)-std::sin(ph);
+        }
+    for (int r = 0; r < 2 * m1; ++r)
+        for (int x = 0; x < H; ++x) {
+            const double th = PI2 * (double)((long)krow(r) * x % H) / H;
+            t2c[(size_t)r * d.Hk + x] = (float)std::cos(th);
+            t2s[(size_t)r * d.Hk + x] = (float)std::sin(th);
+        }
+    std::vector<float> inv((size_t)d.K2 * d.Wq + 2 * (size_t)d.Hp * d.R4, 0.f);
+    float* tb = inv.data();
+    float* tac = tb + (size_t)d.K2 * d.Wq;
+    float* tas = tac + (size_t)d.Hp * d.R4;
+    for (int l = 0; l < m2; ++l)
+        for (int y = 0; y < W; ++y) {
+            const double cl = hermitian_scale(l, H, W), ph = PI2 * (double)((long)l * y % W) / W;
+            tb[(size_t)l * d.Wq + y] = (float)(cl * std::cos(ph));
+            tb[(size_t)(m2 + l) * d.Wq + y] = (float)(-cl * std::sin(ph));
+        }
+    for (int x = 0; x < H; ++x)
+        for (int r = 0; r < 2 * m1; ++r) {
+            const double th = PI2 * (double)((long)krow(r) * x % H) / H;
+            tac[(size_t)x * d.R4 + r] = (float)std::cos(th);
+            tas[(size_t)x * d.R4 + r] = (float)std::sin(th);
+        }
+    std::vector<float> clhw(m2);
+    for (int l = 0; l < m2; ++l) clhw[l] = (float)hermitian_scale(l, H, W);
+    std::vector<float> gx, gy;
+    make_grids(H, W, gx, gy);
+    int rc = upload(fwd, &p->d_many_fwd);
+    if (rc == CFD_OK) rc = upload(inv, &p->d_many_inv);
+    if (rc == CFD_OK) rc = upload(clhw, &p->d_clhw);
+    if (rc == CFD_OK) rc = upload(gx, &p->d_gx);
+    if (rc == CFD_OK) rc = upload(gy, &p->d_gy);
+    if (rc != CFD_OK) {
+        cfd_set_error("cfd_plan_create: device allocation/copy of operator tables failed");
+        cfd_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return CFD_OK;
+}
+
 extern "C" int cfd_plan_create(int H, int W, int m1, int m2, cfd_plan** out) {
     CFD_REQUIRE(out != nullptr, CFD_ERR_INVALID_ARG, "cfd_plan_create: out is NULL");
     CFD_REQUIRE(H >= 2 && H <= 128 && W >= 2 && W <= 80, CFD_ERR_UNSUPPORTED,
                 "cfd_plan_create: grid %dx%d unsupported (need 2<=H<=128, 2<=W<=80)", H, W);
-    CFD_REQUIRE(m1 >= 1 && m1 <= 15 && 2 * m1 <= H, CFD_ERR_UNSUPPORTED,
-                "cfd_plan_create: modes1=%d unsupported (need 1<=m1<=15 and 2*m1<=H=%d)", m1, H);
-    CFD_REQUIRE(m2 >= 1 && m2 <= 16 && m2 <= W / 2 + 1, CFD_ERR_UNSUPPORTED,
-                "cfd_plan_create: modes2=%d unsupported (need 1<=m2<=16 and m2<=W/2+1, W=%d)", m2, W);
+    CFD_REQUIRE(m1 >= 1 && 2 * m1 <= H, CFD_ERR_UNSUPPORTED,
+                "cfd_plan_create: modes1=%d unsupported (need 1<=m1 and 2*m1<=H=%d)", m1, H);
+    CFD_REQUIRE(m2 >= 1 && m2 <= W / 2 + 1, CFD_ERR_UNSUPPORTED,
+                "cfd_plan_create: modes2=%d unsupported (need 1<=m2<=W/2+1, W=%d)", m2, W);
+    if (m1 > 15 || m2 > 16) return cfd_plan_create_many(H, W, m1, m2, out);
     cfd_plan* p = new cfd_plan();
     p->H = H; p->W = W; p->m1 = m1; p->m2 = m2;
     p->NJ = (W + 15) / 16;
@@ -115,10 +194,8 @@ extern "C" int cfd_plan_create(int H, int W, int m1, int m2, cfd_plan** out) {
                 const double ph = PI2 * (double)((long)l * y % W) / W;
                 tb[(s * NJ + j) * 64 + lane] = (float)(im ? -cl * std::sin(ph) : cl * std::cos(ph));
             }
-    // ---- coordinate grids: np.linspace(0, 1, n) in float64, cast to float32 (fno2d.py:251,253) ----
-    std::vector<float> gx(H), gy(W);
-    for (int i = 0; i < H; ++i) gx[i] = (i == H - 1) ? 1.0f : (float)((double)i * (1.0 / (double)(H - 1)));
-    for (int i = 0; i < W; ++i) gy[i] = (i == W - 1) ? 1.0f : (float)((double)i * (1.0 / (double)(W - 1)));
+    std::vector<float> gx, gy;
+    make_grids(H, W, gx, gy);
 
     // a table value in CFD_TW = 3 bf16 pieces (hi, lo, lo2: exact), written at 16-byte vector `vec` (+64, +128 for the later pieces)
     auto put3 = [&](std::vector<unsigned short>& dst, size_t vec, int v, double x) {
@@ -285,6 +362,8 @@ extern "C" void cfd_plan_destroy(cfd_plan* p) {
     if (p->d_fwd_g) hipFree(p->d_fwd_g);
     if (p->d_inv_g) hipFree(p->d_inv_g);
     if (p->d_tail) hipFree(p->d_tail);
+    if (p->d_many_fwd) hipFree(p->d_many_fwd);
+    if (p->d_many_inv) hipFree(p->d_many_inv);
     hipFree(p->d_clhw);
     hipFree(p->d_gx);
     hipFree(p->d_gy);

@@ -693,7 +693,7 @@ bool cfd_int_dft_stem_ok(const cfd_plan* p, int B, int in_chan, int P, int C, co
     // workgroups per CU: nine dependent L2 round trips per image) -- step 1.227 against 1.224 ms, no gain -- but a 64-case rollout step
     // goes from 196.4 to 191.6 us.  Default: below 128 entries; "stem_dft" = 1 everywhere, 0 never.
     const int knob = cfd_tune_get(CFD_TUNE_STEM_DFT);
-    if (knob == 0 || B < 1 || (knob != 1 && B >= 128)) return false;
+    if (knob == 0 || B < 1 || (knob != 1 && B >= 128) || p->many) return false;
     if (!(p->W == 64 && p->H == 64 && p->NJ == 4 && p->d_fwd_b3) || cfd_tune_get(CFD_TUNE_EXACT_FP32) == 1) return false;
     if (in_chan != 2 || P < 0 || P > 8 || C < 1 || C > 32) return false;
     return (((uintptr_t)inputs | (uintptr_t)mask | (uintptr_t)a0 | (uintptr_t)p->d_gy) % 16) == 0;
@@ -722,6 +722,8 @@ int cfd_int_spectral_dft_stem(const cfd_plan* p, const float* inputs, const floa
 int cfd_int_spectral_dft(const cfd_plan* p, const void* x, float* xh, int nimg, int act_in, int dt, void* stream) {
     if (dt == CFD_DT_F32) return cfd_spectral_dft(p, (const float*)x, xh, nimg, act_in, stream);
     CFD_REQUIRE(p && x && xh && nimg >= 0, CFD_ERR_INVALID_ARG, "cfd_spectral_dft: NULL pointer or negative count");
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_dft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
+                p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(act_in ? "k_dft_fwd_act" : "k_dft_fwd", st, (double)nimg * (2.0 * p->H * p->W + 16.0 * p->m1 * p->m2),
@@ -735,6 +737,7 @@ int cfd_int_spectral_dft(const cfd_plan* p, const void* x, float* xh, int nimg, 
 extern "C" int cfd_spectral_dft(const cfd_plan* p, const float* x, float* xh, int nimg, int act_in, void* stream) {
     CFD_REQUIRE(p && x && xh && nimg >= 0, CFD_ERR_INVALID_ARG, "cfd_spectral_dft: NULL pointer or negative count");
     if (nimg == 0) return CFD_OK;
+    if (p->many) return cfd_int_dft_many(p, x, xh, nimg, act_in, stream);  // dft_many.hip
     hipStream_t st = (hipStream_t)stream;
     if (p->NJ == 4) {
         if (p->W % 4 == 0 && ((uintptr_t)x % 16) == 0) return launch_dft<4, true>(p, x, xh, nimg, act_in, st);
@@ -1893,7 +1896,7 @@ static bool launch_idft_g(const cfd_plan* p, const float* z, const TADD* addend,
 }
 
 static bool idft64_applies(const cfd_plan* p) {
-    return p->W == 64 && p->H % 16 == 0 && p->d_inv_b3 && 4 * p->m1 * p->m2 + 1 <= CFD_BLK_ZS &&
+    return !p->many && p->W == 64 && p->H % 16 == 0 && p->d_inv_b3 && 4 * p->m1 * p->m2 + 1 <= CFD_BLK_ZS &&
            cfd_tune_get(CFD_TUNE_EXACT_FP32) != 1;
 }
 
@@ -1957,6 +1960,8 @@ int cfd_int_spectral_idft(const cfd_plan* p, const float* z, const void* addend,
     if (dt == CFD_DT_F32) return cfd_spectral_idft(p, z, (const float*)addend, (const float*)aprev, (float*)out, nimg, epi, stream);
     CFD_REQUIRE(p && z && out && nimg >= 0 && epi >= 0 && epi <= 2 && (epi < 1 || addend) && (epi < 2 || aprev), CFD_ERR_INVALID_ARG,
                 "cfd_spectral_idft: bad arguments");
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
+                p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
@@ -1973,6 +1978,8 @@ int cfd_int_spectral_idft_grad(const cfd_plan* p, const float* z, const float* a
     const int epi = aprev ? 2 : 1;
     if (dt == CFD_DT_F32) return cfd_spectral_idft(p, z, addend, (const float*)aprev, out, nimg, epi, stream);
     CFD_REQUIRE(p && z && out && addend && nimg >= 0, CFD_ERR_INVALID_ARG, "cfd_spectral_idft(grad): bad arguments");
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft(grad): bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
+                p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(epi == 1 ? "k_idft_add" : "k_idft_add_dgelu", st,
@@ -1989,6 +1996,7 @@ extern "C" int cfd_spectral_idft(const cfd_plan* p, const float* z, const float*
     CFD_REQUIRE(epi >= 0 && epi <= 2, CFD_ERR_INVALID_ARG, "cfd_spectral_idft: epi must be 0,1,2");
     CFD_REQUIRE(epi < 1 || addend, CFD_ERR_INVALID_ARG, "cfd_spectral_idft: epi>=1 needs addend");
     CFD_REQUIRE(epi < 2 || aprev, CFD_ERR_INVALID_ARG, "cfd_spectral_idft: epi==2 needs aprev");
+    if (p->many) return cfd_int_idft_many(p, z, addend, aprev, out, nimg, epi, stream);  // dft_many.hip
     CFD_REQUIRE(p->T <= 8 && p->SA <= 8 && p->SB <= 8, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft: plan too large");
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -2476,6 +2484,7 @@ static bool block_is_gen(const cfd_plan* p) { return p->W != 64 || p->H % 16 != 
 // B = batch entries, bwd = the input-gradient direction (c != NULL: with gelu')
 static bool block_fused_ok(const cfd_plan* p, int Cs, int Cd, const void* a, const void* b, const void* c, const void* z, int B, bool bwd) {
     const int cmax = Cs > Cd ? Cs : Cd;
+    if (p->many) return false;  // many-modes plans: the two passes (1x1 conv + dft_many.hip's inverse with addend)
     if (cfd_tune_get(CFD_TUNE_EXACT_FP32) == 1 || !p->d_inv_b3 || p->T > CFD_KB_TMAX) return false;  // (the fused kernel's inverse transform is split-bf16)
     if (4 * p->m1 * p->m2 + 1 > CFD_BLK_ZS || cmax > 32 || ((uintptr_t)z % 16) != 0) return false;
     // 25 .. 32 channels (the reference's default width 32).  Round 5: two (8,2,4) workgroups per entry re-read every source value from
@@ -2654,7 +2663,7 @@ __global__ __launch_bounds__(256) void k_stem_grad_combine(const float* __restri
 // whether the input gradient of FnoBlock 0 can emit the lifting layer's sums instead of storing g_0 (same predicate in both phases)
 bool cfd_int_stemg_ok(const cfd_plan* p, int B, int C, int in_chan, int P, const void* inputs, const void* mask, const void* z) {
     if (cfd_tune_get(CFD_TUNE_STEM_FUSE) == 0) return false;
-    if (!p || C > 24 || in_chan < 1 || in_chan > 2 || P > 8 || B < 1) return false;
+    if (!p || p->many || C > 24 || in_chan < 1 || in_chan > 2 || P > 8 || B < 1) return false;
     if (cfd_tune_get(CFD_TUNE_EXACT_FP32) == 1 || !p->d_inv_b3 || p->T > CFD_KB_TMAX || 4 * p->m1 * p->m2 + 1 > CFD_BLK_ZS) return false;
     if (((uintptr_t)z % 16) != 0) return false;
     if (block_is_gen(p))  // general grids (66 x 65): built and tested, but OFF unless stem_fuse = 3 -- with the ragged tile and the tail column

@@ -295,6 +295,9 @@ class FnoTrainEngine:
         # launch).  Data-parallel steps keep them: a rank's gradients must be final and normalised by ITS labels before the all-reduce.
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
         self.defer_flags = 0 if (self.sync.exchange or not fused_head) else 7
+        # the wide-channel route (hidden > 32) and the many-modes route (modes1 > 15 or modes2 > 16) have none of the fused kernels and
+        # ignore the flags (fno.cpp: deferred()): their gradients are final after the pass
+        self._route_defers = self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.scores_buf = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -397,7 +400,7 @@ class FnoTrainEngine:
                           self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
                           self.step_count, grad_scale, self.loss_id, self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
             self._last = (inputs, case_params, mask, 0)  # (a second optimizer_step on the same gradients must not redo the deferred work)
-            self._grad_pending_scale = bool(flags & 1) and self.loss_id == _LOSS_IDS["nmse"]
+            self._grad_pending_scale = bool(flags & 1) and self.loss_id == _LOSS_IDS["nmse"] and self._route_defers
             return
         self._grad_pending_scale = False
         self.api.call("cfd_adam_flat", self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),

@@ -62,6 +62,9 @@ int cfd_prof_end(char* buf, size_t cap);
 /* ---- plan: pruned-DFT operator tables for one grid (H,W) and mode count (m1,m2) -------------------------
  * Replaces the implicit FFT plans behind torch.fft.rfft2 / irfft2 (src/models/fno/fno2d.py:62,81) and the
  * per-call host-side np.linspace coordinate grids of Fno2d.get_coords (fno2d.py:244-255).
+ * Grids 2 <= H <= 128, 2 <= W <= 80; modes 1 <= m1 with 2*m1 <= H, 1 <= m2 <= W/2+1 (the reference's range, fno2d.py:59-82).
+ * m1 <= 15 and m2 <= 16 is the narrow route (spectral.hip); any other plan is a many-modes plan (dft_many.hip): fp32 activation
+ * storage only, no FnoBlock / lifting-layer fusion.
  * Allocates a few tens of KB of device memory; create once per (H,W,m1,m2), never inside stream capture. */
 typedef struct cfd_plan cfd_plan;
 int cfd_plan_create(int H, int W, int m1, int m2, cfd_plan** out);
