@@ -11,6 +11,10 @@
  *     (cfd_last_error() gives the text); no C++ exception crosses the boundary;
  *   - all buffers are owned by the caller (PyTorch's caching allocator); any scratch is a caller-provided
  *     workspace whose size the matching *_workspace_bytes() function reports;
+ *   - outputs and workspaces need NO initialisation: unless an entry point says that a buffer is an input, carries state or is
+ *     accumulated into, every element of an output is written (never added to), a workspace may hold anything on entry (stale
+ *     values of an earlier call at another shape included), and nothing outside the declared sizes is written
+ *     (tests/backends.py allocates accordingly: poisoned outputs and workspaces between guard bands);
  *   - fp32 tensors are NCHW-contiguous; complex64 tensors are interleaved (re,im) float pairs, exactly
  *     torch.view_as_real of the reference's parameters (state_dict ABI);
  *   - functions are re-entrant; a cfd_plan is immutable after creation and may be shared between threads;
@@ -220,7 +224,9 @@ int cfd_gelu_fwd(const float* x, float* y, size_t n, void* stream);
 int cfd_gelu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stream);
 
 /* torch.optim.Adam step on one flat fp32 buffer (train_auto.py:213,256; complex params as (re,im) pairs --
- * torch's view_as_real handling).  step >= 1.                                                               */
+ * torch's view_as_real handling).  step >= 1.  param is updated in place; exp_avg / exp_avg_sq are the optimizer's state: read and
+ * updated in place by every call, so the caller zeroes them before step 1 and leaves them alone afterwards (cfd_adam_multi and
+ * cfd_fno_adam_step alike).  grad is read only.                                                                */
 int cfd_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 /* The same step for n parameter tensors in one launch per 80 tensors (host tables of device pointers and element counts).  lr_dev /
@@ -523,7 +529,9 @@ int cfd_fno_backward_phase_ex(const cfd_plan* plan, const cfd_fno_shape* shape, 
  * calls alike, they evaluate the same predicates -- so the caller passes the same `flags` to the forward, to every phase and to
  * cfd_fno_adam_step.  flags = 0 is exactly cfd_fno_forward_train_ex / cfd_fno_backward_phase_ex / cfd_adam_flat.  Data-parallel
  * training keeps flags = 0: a rank's gradients must be final and normalised by ITS labels before they are all-reduced.
- * cfd_fno_adam_step: param / grad / exp_avg / exp_avg_sq = the flat buffers (n floats) that `params` / `grads` point into.       */
+ * cfd_fno_adam_step: param / grad / exp_avg / exp_avg_sq = the flat buffers (n floats) that `params` / `grads` point into.  The backward
+ * phases write every gradient TENSOR; elements of the flat buffers that belong to no tensor (alignment padding between tensors) are read
+ * and updated like any other: the caller zeroes them once, nothing writes them afterwards.                                          */
 #define CFD_TRAIN_DEFER_SCALE 1
 #define CFD_TRAIN_DEFER_HEAD 2
 #define CFD_TRAIN_DEFER_STEM 4

@@ -24,6 +24,11 @@ def nm(a, ref):
     return O.rel_nmse(a, ref)
 
 
+def nan_max(*vals):
+    """The largest of `vals`, NaN if any is NaN (Python's max() drops a NaN that is not its first argument)."""
+    return float(np.max(np.asarray([float(v) for v in vals], dtype=np.float64)))
+
+
 @contextlib.contextmanager
 def tuned(be, **knobs):
     """Dispatch overrides (cfd_tune_set) for the duration of a check; -1 restores the built-in choice."""
@@ -46,19 +51,19 @@ def check_spectral(be, B, Cin, Cout, H, W, m1=12, m2=12, seed=0):
     plan = api.plan_create(H, W, m1, m2)
     try:
         dx, dgy, dw1, dw2 = be.dev(x), be.dev(gy), be.dev(w1), be.dev(w2)
-        xh = be.zeros((B, Cin, 2 * m1, m2), np.complex64)
-        z = be.zeros((B, Cout, 2 * m1, m2), np.complex64)
-        y = be.zeros((B, Cout, H, W))
+        xh = be.out((B, Cin, 2 * m1, m2), np.complex64)
+        z = be.out((B, Cout, 2 * m1, m2), np.complex64)
+        y = be.out((B, Cout, H, W))
         api.call("cfd_spectral_conv2d_fwd", plan, P(dx), P(dw1), P(dw2), P(y), P(xh), P(z), B, Cin, Cout, be.stream)
         be.sync()
         x64, w164, w264 = x.astype(f64), w1.astype(c128), w2.astype(c128)
         res = {}
         res["xh"] = nm(be.host(xh), O.pruned_dft_fwd(x64, m1, m2))
         res["y"] = nm(be.host(y), O.spectral_conv2d_fwd(x64, w164, w264))
-        ws = be.bytes(api.size("cfd_spectral_conv2d_bwd_workspace_bytes", plan, B, Cin, Cout))
-        gx = be.zeros((B, Cin, H, W))
-        gw1 = be.zeros((Cin, Cout, m1, m2), np.complex64)
-        gw2 = be.zeros((Cin, Cout, m1, m2), np.complex64)
+        ws = be.scratch(api.size("cfd_spectral_conv2d_bwd_workspace_bytes", plan, B, Cin, Cout))
+        gx = be.out((B, Cin, H, W))
+        gw1 = be.out((Cin, Cout, m1, m2), np.complex64)
+        gw2 = be.out((Cin, Cout, m1, m2), np.complex64)
         api.call("cfd_spectral_conv2d_bwd", plan, P(dgy), P(xh), P(dw1), P(dw2), P(gx), P(gw1), P(gw2), P(ws), B, Cin,
                  Cout, be.stream)
         be.sync()
@@ -86,18 +91,18 @@ def check_mix_wgrad(be, B, Cin, Cout, m1=12, m2=12, H=64, W=64, seed=11):
     plan = api.plan_create(H, W, m1, m2)
     try:
         dxh, dgh, dw1, dw2 = be.dev(xh), be.dev(gh), be.dev(w1), be.dev(w2)
-        z = be.zeros((B, Cout, *M2), np.complex64)
+        z = be.out((B, Cout, *M2), np.complex64)
         api.call("cfd_spectral_mix", plan, P(dxh), P(dw1), P(dw2), P(z), B, Cin, Cout, 0, be.stream)
-        gz = be.zeros((B, Cin, *M2), np.complex64)
+        gz = be.out((B, Cin, *M2), np.complex64)
         api.call("cfd_spectral_mix", plan, P(dgh), P(dw1), P(dw2), P(gz), B, Cin, Cout, 1, be.stream)
-        ws = be.bytes(api.size("cfd_spectral_wgrad_workspace_bytes", plan, B, Cin, Cout))
-        gw1 = be.zeros((Cin, Cout, m1, m2), np.complex64)
-        gw2 = be.zeros((Cin, Cout, m1, m2), np.complex64)
+        ws = be.scratch(api.size("cfd_spectral_wgrad_workspace_bytes", plan, B, Cin, Cout))
+        gw1 = be.out((Cin, Cout, m1, m2), np.complex64)
+        gw2 = be.out((Cin, Cout, m1, m2), np.complex64)
         api.call("cfd_spectral_wgrad", plan, P(dxh), P(dgh), P(gw1), P(gw2), P(ws), B, Cin, Cout, be.stream)
         # the two gradient-mode consumers in one call (one launch where the fused kernel applies)
-        fgz = be.zeros((B, Cin, *M2), np.complex64)
-        fgw1 = be.zeros((Cin, Cout, m1, m2), np.complex64)
-        fgw2 = be.zeros((Cin, Cout, m1, m2), np.complex64)
+        fgz = be.out((B, Cin, *M2), np.complex64)
+        fgw1 = be.out((Cin, Cout, m1, m2), np.complex64)
+        fgw2 = be.out((Cin, Cout, m1, m2), np.complex64)
         api.call("cfd_spectral_mix_adj_wgrad", plan, P(dxh), P(dgh), P(dw1), P(dw2), P(fgz), P(fgw1), P(fgw2), P(ws), B,
                  Cin, Cout, be.stream)
         be.sync()
@@ -135,18 +140,18 @@ def check_block(be, B, Cin, Cout, H, W, m1=12, m2=12, seed=12):
         res = {}
         a64, w64 = a.astype(f64), w0.astype(f64)
         for act in (0, 1):
-            out = be.zeros((B, Cout, H, W))
+            out = be.out((B, Cout, H, W))
             api.call("cfd_fno_block_fwd", plan, P(da), P(dz), P(dw), P(db), P(out), B, Cin, Cout, act, be.stream)
             be.sync()
             fa = O.gelu(a64) if act else a64
             ref = np.einsum("oi,bixy->boxy", w64, fa) + b0[None, :, None, None] + O.pruned_idft(z.astype(c128), H, W)
             res[f"fwd_act{act}"] = nm(be.host(out), ref)
         refg = np.einsum("oi,boxy->bixy", w64, g.astype(f64)) + O.pruned_idft(gz.astype(c128), H, W)
-        gin = be.zeros((B, Cin, H, W))
+        gin = be.out((B, Cin, H, W))
         api.call("cfd_fno_block_bwd_input", plan, P(dg), P(dgz), P(dw), None, P(gin), B, Cin, Cout, be.stream)
         be.sync()
         res["bwd"] = nm(be.host(gin), refg)
-        gin2 = be.zeros((B, Cin, H, W))
+        gin2 = be.out((B, Cin, H, W))
         api.call("cfd_fno_block_bwd_input", plan, P(dg), P(dgz), P(dw), P(da), P(gin2), B, Cin, Cout, be.stream)
         be.sync()
         res["bwd_dgelu"] = nm(be.host(gin2), refg * O.gelu_grad(a64))
@@ -172,7 +177,7 @@ def check_block_batch_split(be, Bbig, Bsmall, C, H, W, m1=12, m2=12, seed=13):
         res = {}
         outs = []
         for B in (Bbig, Bsmall):
-            out, gin = be.zeros((B, C, H, W)), be.zeros((B, C, H, W))
+            out, gin = be.out((B, C, H, W)), be.out((B, C, H, W))
             api.call("cfd_fno_block_fwd", plan, P(da), P(dz), P(dw), P(db), P(out), B, C, C, 1, be.stream)
             api.call("cfd_fno_block_bwd_input", plan, P(dg), P(dz), P(dw), P(da), P(gin), B, C, C, be.stream)
             be.sync()
@@ -204,7 +209,7 @@ def check_idft_epilogues(be, nimg, H, W, m1=12, m2=12, seed=1):
         be.sync()
         res["epi2"] = nm(be.host(o2), (ref + ad) * O.gelu_grad(ap.astype(f64)))
         # GELU-on-load variant of the forward transform
-        xh = be.zeros((nimg, 1, 2 * m1, m2), np.complex64)
+        xh = be.out((nimg, 1, 2 * m1, m2), np.complex64)
         api.call("cfd_spectral_dft", plan, P(dap), P(xh), nimg, 1, be.stream)
         be.sync()
         res["dft_gelu"] = nm(be.host(xh), O.pruned_dft_fwd(O.gelu(ap.astype(f64)), m1, m2))
@@ -222,17 +227,17 @@ def check_chanmix(be, B, Ci, Co, HW, act, seed=2):
     g = rng.standard_normal((B, Co, HW)).astype(np.float32)
     f = O.gelu(x.astype(f64)) if act else x.astype(f64)
     res = {}
-    out = be.zeros((B, Co, HW))
+    out = be.out((B, Co, HW))
     dx, dw, db, dg = be.dev(x), be.dev(w), be.dev(b), be.dev(g)  # keep alive across the calls
     api.call("cfd_chanmix", P(dx), P(dw), P(db), P(out), B, Ci, Co, HW, int(act), 0, be.stream)
     be.sync()
     res["fwd"] = nm(be.host(out), np.einsum("oi,bip->bop", w.astype(f64), f) + b[None, :, None])
-    gin = be.zeros((B, Ci, HW))
+    gin = be.out((B, Ci, HW))
     api.call("cfd_chanmix", P(dg), P(dw), None, P(gin), B, Co, Ci, HW, 0, 1, be.stream)
     be.sync()
     res["bwd_in"] = nm(be.host(gin), np.einsum("oi,bop->bip", w.astype(f64), g.astype(f64)))
-    ws = be.bytes(api.size("cfd_chan_wgrad_workspace_bytes", B, Ci, Co, HW))
-    gw, gb = be.zeros((Co, Ci)), be.zeros((Co,))
+    ws = be.scratch(api.size("cfd_chan_wgrad_workspace_bytes", B, Ci, Co, HW))
+    gw, gb = be.out((Co, Ci)), be.out((Co,))
     api.call("cfd_chan_wgrad", P(dg), P(dx), P(gw), P(gb), P(ws), B, Ci, Co, HW, int(act), be.stream)
     be.sync()
     res["gw"] = nm(be.host(gw), np.einsum("bop,bip->oi", g.astype(f64), f))
@@ -252,19 +257,19 @@ def check_stem(be, B, H, W, P_, C, border, seed=3):
     try:
         feats = O.assemble_features(batch["inputs"].astype(f64), batch["case_params"].astype(f64), batch["mask"].astype(f64))
         res = {}
-        out = be.zeros((B, C, H, W))
+        out = be.out((B, C, H, W))
         di, dm, dc = be.dev(batch["inputs"]), be.dev(batch["mask"]), be.dev(batch["case_params"])
         dw, db, dg = be.dev(w), be.dev(b), be.dev(g)
         api.call("cfd_fno_stem_fwd", plan, P(di), P(dm), P(dc), P(dw), P(db), P(out), B, 2, P_, C, be.stream)
         be.sync()
         res["fwd"] = nm(be.host(out), O.conv1x1(feats, w.astype(f64), b.astype(f64)))
-        out2 = be.zeros((B, C, H, W))
+        out2 = be.out((B, C, H, W))
         api.call("cfd_fno_stem_fwd", plan, P(di), None, P(dc), P(dw), P(db), P(out2), B, 2, P_, C, be.stream)
         be.sync()
         feats1 = O.assemble_features(batch["inputs"].astype(f64), batch["case_params"].astype(f64), np.ones_like(batch["mask"], dtype=f64))
         res["fwd_nomask"] = nm(be.host(out2), O.conv1x1(feats1, w.astype(f64), b.astype(f64)))
-        ws = be.bytes(api.size("cfd_fno_stem_bwd_workspace_bytes", plan, B, 2, P_, C))
-        gw, gb = be.zeros((C, F)), be.zeros((C,))
+        ws = be.scratch(api.size("cfd_fno_stem_bwd_workspace_bytes", plan, B, 2, P_, C))
+        gw, gb = be.out((C, F)), be.out((C,))
         api.call("cfd_fno_stem_bwd", plan, P(dg), P(di), P(dm), P(dc), P(gw), P(gb), P(ws), B, 2, P_, C, be.stream)
         be.sync()
         res["gw"] = nm(be.host(gw), np.einsum("bohw,bihw->oi", g.astype(f64), feats))
@@ -303,9 +308,9 @@ def check_head(be, B, C, HW, act, which="nmse", with_ext=False, border=True, see
     res = {}
     da, dm, dl = be.dev(a), be.dev(mask), be.dev(label)
     dw1, db1, dw2, db2 = be.dev(w1), be.dev(b1), be.dev(w2), be.dev(b2)
-    ws = be.bytes(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW))
-    preds = be.zeros((B, Co, HW))
-    sums = be.zeros((4,))
+    ws = be.scratch(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW))
+    preds = be.out((B, Co, HW))
+    sums = be.out((4,))
     api.call("cfd_fno_head_fwd", P(da), P(dm), P(dl), P(dw1), P(db1), P(dw2), P(db2), P(preds), P(sums), P(ws), B, C, Hd, Co,
              HW, int(act), be.stream)
     be.sync()
@@ -313,15 +318,15 @@ def check_head(be, B, C, HW, act, which="nmse", with_ext=False, border=True, see
     d = preds_ref - lab_m
     sref = np.array([np.sum(d * d), np.sum(np.abs(d)), np.sum(lab_m * lab_m), d.size])
     res["sums"] = float(np.max(np.abs(be.host(sums) - sref) / np.abs(sref)))
-    scores = be.zeros((4,))
+    scores = be.out((4,))
     api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
     be.sync()
     lr = O.mse_loss(preds_ref, lab_m, True)
     sc = be.host(scores)
-    res["scores"] = float(max(abs(sc[0] - lr["mse"]) / lr["mse"], abs(sc[1] - lr["rmse"]) / lr["rmse"],
-                              abs(sc[2] - lr["mae"]) / lr["mae"], abs(sc[3] - lr["nmse"]) / lr["nmse"]))
+    res["scores"] = nan_max(abs(sc[0] - lr["mse"]) / lr["mse"], abs(sc[1] - lr["rmse"]) / lr["rmse"],
+                            abs(sc[2] - lr["mae"]) / lr["mae"], abs(sc[3] - lr["nmse"]) / lr["nmse"])
     # backward
-    coef = be.zeros((2,))
+    coef = be.out((2,))
     api.call("cfd_loss_coef", P(sums), P(coef), {"mse": 0, "nmse": 1, "mae": 2}[which], 1.0, be.stream)
     gp = O.loss_grad_wrt_preds(preds_ref, lab_m, which)
     if with_ext:
@@ -331,8 +336,8 @@ def check_head(be, B, C, HW, act, which="nmse", with_ext=False, border=True, see
     gz = ga1 * O.gelu_grad(z1)
     gh = np.einsum("ji,bjp->bip", w1.astype(f64), gz)
     ga_ref = gh * O.gelu_grad(A) if act else gh
-    ga = be.zeros((B, C, HW))
-    gw1, gb1, gw2, gb2 = be.zeros((Hd, C)), be.zeros((Hd,)), be.zeros((Co, Hd)), be.zeros((Co,))
+    ga = be.out((B, C, HW))
+    gw1, gb1, gw2, gb2 = be.out((Hd, C)), be.out((Hd,)), be.out((Co, Hd)), be.out((Co,))
     dgext = be.dev(gext) if with_ext else None
     api.call("cfd_fno_head_bwd", P(da), P(dm), P(dl), P(preds), P(dgext), P(coef), P(dw1),
              P(db1), P(dw2), P(ga), P(gw1), P(gb1), P(gw2), P(gb2), P(ws), B, C, Hd, Co, HW, int(act), be.stream)
@@ -365,12 +370,13 @@ def check_head_train(be, B, C, HW, act, which="nmse", border=True, seed=14):
     lab_m = Lb * M
     da, dm, dl = be.dev(a), be.dev(mask), be.dev(label)
     dw1, db1, dw2, db2 = be.dev(w1), be.dev(b1), be.dev(w2), be.dev(b2)
-    ws = be.bytes(max(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW), api.size("cfd_label_energy_workspace_bytes")))
-    preds, sums, coef = be.zeros((B, Co, HW)), be.zeros((4,)), be.zeros((2,))
-    ga = be.zeros((B, C, HW))
-    gw1, gb1, gw2, gb2 = be.zeros((Hd, C)), be.zeros((Hd,)), be.zeros((Co, Hd)), be.zeros((Co,))
+    ws = be.scratch(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW))
+    wse = be.scratch(api.size("cfd_label_energy_workspace_bytes"))  # (its own: each entry point on a workspace of exactly its size)
+    preds, sums, coef = be.out((B, Co, HW)), be.out((4,)), be.out((2,))
+    ga = be.out((B, C, HW))
+    gw1, gb1, gw2, gb2 = be.out((Hd, C)), be.out((Hd,)), be.out((Co, Hd)), be.out((Co,))
     wid = {"mse": 0, "nmse": 1, "mae": 2}[which]
-    api.call("cfd_label_energy_coef", P(dl), P(dm), P(sums), P(coef), P(ws), B, Co, HW, wid, 1.0, be.stream)
+    api.call("cfd_label_energy_coef", P(dl), P(dm), P(sums), P(coef), P(wse), B, Co, HW, wid, 1.0, be.stream)
     api.call("cfd_fno_head_train", P(da), P(dm), P(dl), P(coef), P(dw1), P(db1), P(dw2), P(db2), P(preds), P(sums), P(ga), P(gw1),
              P(gb1), P(gw2), P(gb2), P(ws), B, C, Hd, Co, HW, int(act), be.stream)
     be.sync()
@@ -395,8 +401,8 @@ def check_loss_and_adam(be, n=10007, seed=5):
     rng = np.random.default_rng(seed)
     p = rng.standard_normal(n).astype(np.float32)
     l = rng.standard_normal(n).astype(np.float32)
-    ws = be.bytes(api.size("cfd_loss_workspace_bytes", n))
-    sums = be.zeros((4,))
+    ws = be.scratch(api.size("cfd_loss_workspace_bytes", n))
+    sums = be.out((4,))
     dpp, dll = be.dev(p), be.dev(l)
     api.call("cfd_masked_loss_sums", P(dpp), P(dll), P(sums), P(ws), n, be.stream)
     be.sync()
@@ -443,22 +449,22 @@ def run_fno(be, params, batch, L, C, H, W, p, with_label=True, which="nmse"):
     try:
         shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.zeros(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
+        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
         ps, gs = make_param_struct(be, pd, L), make_param_struct(be, gd, L)
-        ws = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
+        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
         di, dc, dm = be.dev(batch["inputs"]), be.dev(batch["case_params"]), be.dev(batch["mask"])
         dl = be.dev(batch["label"]) if with_label else None
-        preds = be.zeros((B, 2, H, W))
-        sums = be.zeros((4,))
+        preds = be.out((B, 2, H, W))
+        sums = be.out((4,))
         api.call("cfd_fno_forward", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds),
                  P(sums), P(ws), 1, be.stream)
         out = {}
         if with_label:
-            coef = be.zeros((2,))
+            coef = be.out((2,))
             api.call("cfd_loss_coef", P(sums), P(coef), {"mse": 0, "nmse": 1, "mae": 2}[which], 1.0, be.stream)
             api.call("cfd_fno_backward", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm),
                      P(dl), P(preds), None, P(coef), P(ws), be.stream)
-            scores = be.zeros((4,))
+            scores = be.out((4,))
             api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
             be.sync()
             out["grads"] = {k: be.host(v) for k, v in gd.items()}
@@ -466,8 +472,8 @@ def run_fno(be, params, batch, L, C, H, W, p, with_label=True, which="nmse"):
         be.sync()
         out["preds"] = be.host(preds)
         # inference-mode workspace (ping-pong activations) must give the same predictions
-        ws0 = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
-        preds0 = be.zeros((B, 2, H, W))
+        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
+        preds0 = be.out((B, 2, H, W))
         api.call("cfd_fno_forward", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), None, P(preds0), None,
                  P(ws0), 0, be.stream)
         be.sync()
@@ -475,6 +481,19 @@ def run_fno(be, params, batch, L, C, H, W, p, with_label=True, which="nmse"):
         return out
     finally:
         api.plan_destroy(plan)
+
+
+def flat_grad_buffer(be, layout, numel):
+    """The flat gradient buffer of the fused training step, hostile where the contract allows: every tensor's elements are poisoned
+    (cfdbench_amd.h, cfd_fno_backward: "every tensor overwritten"), the alignment padding between tensors is zero (cfd_fno_adam_step:
+    "elements of the flat buffers that belong to no tensor are read and updated like any other: the caller zeroes them once")."""
+    from tests.backends import poison
+    g = poison((numel,)).copy()
+    used = np.zeros(numel, bool)
+    for off, n in layout.values():
+        used[off:off + n] = True
+    g[~used] = 0.0
+    return be.dev(g)
 
 
 def _flat_struct(be, flat, layout, L):
@@ -517,11 +536,12 @@ def check_fno_train_step_deferred(be, B, C, L, H, W, p=5, which="nmse", flags=7,
         di, dc, dm, dl = be.dev(batch["inputs"]), be.dev(batch["case_params"]), be.dev(batch["mask"]), be.dev(batch["label"])
         out = {}
         for fl in (0, flags):
-            flat, grad = be.dev(flat0), be.zeros((numel,))
+            flat, grad = be.dev(flat0), flat_grad_buffer(be, layout, numel)
+            # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
             m, v = be.zeros((numel,)), be.zeros((numel,))
             ps, gs = _flat_struct(be, flat, layout, L), _flat_struct(be, grad, layout, L)
-            ws = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-            preds, sums, coef = be.zeros((B, 2, H, W)), be.zeros((4,)), be.zeros((2,))
+            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
+            preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
             g1 = None
             for step in range(1, steps + 1):
                 api.call("cfd_fno_forward_train_f", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm), P(dl),
@@ -607,8 +627,8 @@ def check_fno_bf16_storage(be, B, C, L, H, W, p=5, border=True, gain=4.0, pseed=
         for name, dt in (("bf16", 1), ("f32", 0)):
             nbytes = api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 0, dt)
             assert nbytes > 0
-            ws = be.bytes(nbytes)
-            preds, sums = be.zeros((B, 2, H, W)), be.zeros((4,))
+            ws = be.scratch(nbytes)
+            preds, sums = be.out((B, 2, H, W)), be.out((4,))
             api.call("cfd_fno_forward_ex", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds),
                      P(sums), P(ws), 0, dt, be.stream)
             be.sync()
@@ -633,8 +653,8 @@ def check_gemm(be, M, N, K, ta, tb, seed=21):
     rng = np.random.default_rng(seed)
     A = rng.standard_normal((K, M) if ta else (M, K)).astype(np.float32)
     Bm = rng.standard_normal((N, K) if tb else (K, N)).astype(np.float32)
-    dA, dB, C = be.dev(A), be.dev(Bm), be.zeros((M, N))
-    ws = be.bytes(api.size("cfd_gemm_workspace_bytes", M, N, K))
+    dA, dB, C = be.dev(A), be.dev(Bm), be.out((M, N))
+    ws = be.scratch(api.size("cfd_gemm_workspace_bytes", M, N, K))
     api.call("cfd_gemm", P(dA), P(dB), P(C), P(ws), M, N, K, A.shape[1], Bm.shape[1], N, int(ta), int(tb), be.stream)
     be.sync()
     ref = (A.T if ta else A).astype(f64) @ (Bm.T if tb else Bm).astype(f64)
@@ -651,14 +671,14 @@ def check_linear(be, M, K, N, act, seed=22):
     b = rng.standard_normal((N,)).astype(np.float32) * 0.3
     gy = rng.standard_normal((M, N)).astype(np.float32)
     dx, dw, db, dgy = be.dev(x), be.dev(w), be.dev(b), be.dev(gy)
-    y, pre = be.zeros((M, N)), be.zeros((M, N))
-    wsf = be.bytes(api.size("cfd_linear_fwd_workspace_bytes", M, K, N))
+    y, pre = be.out((M, N)), be.out((M, N))
+    wsf = be.scratch(api.size("cfd_linear_fwd_workspace_bytes", M, K, N))
     api.call("cfd_linear_fwd", P(dx), P(dw), P(db), P(y), P(pre), P(wsf), M, K, N, code, be.stream)
     be.sync()
     z = x.astype(f64) @ w.astype(f64).T + b
     res = {"y": nm(be.host(y), D.act(z, act)), "pre": nm(be.host(pre), z)}
-    gx, gw, gb = be.zeros((M, K)), be.zeros((N, K)), be.zeros((N,))
-    ws = be.bytes(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
+    gx, gw, gb = be.out((M, K)), be.out((N, K)), be.out((N,))
+    ws = be.scratch(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
     api.call("cfd_linear_bwd", P(dgy), P(dx), P(dw), P(y), P(pre), P(gx), P(gw), P(gb), P(ws), M, K, N, code, be.stream)
     be.sync()
     gz = gy.astype(f64) * D.act_grad(z, act)
@@ -683,9 +703,9 @@ def check_ffn_stack(be, R, dims, act, act_last=False, with_gx=True, seed=29):
     gy = rng.standard_normal((R, dims[L])).astype(np.float32)
     dx, dgy = be.dev(x), be.dev(gy)
     dws, dbs = [be.dev(w) for w in ws], [be.dev(b) for b in bs]
-    ys = [be.zeros((R, d)) for d in dims[1:]]
+    ys = [be.out((R, d)) for d in dims[1:]]
     acted = [code != 0 and (l + 1 < L or act_last) for l in range(L)]
-    zs = [be.zeros((R, dims[l + 1])) if (code >= 3 and acted[l]) else None for l in range(L)]
+    zs = [be.out((R, dims[l + 1])) if (code >= 3 and acted[l]) else None for l in range(L)]
     arr = lambda ts: (ctypes.c_void_p * len(ts))(*[P(t) for t in ts])  # noqa: E731
     cdims = (ctypes.c_int * (L + 1))(*dims)
     api.call("cfd_ffn_stack_fwd", P(dx), arr(dws), arr(dbs), arr(ys), arr(zs), R, cdims, L, code, int(act_last), be.stream)
@@ -701,9 +721,9 @@ def check_ffn_stack(be, R, dims, act, act_last=False, with_gx=True, seed=29):
     for l in range(L):
         if zs[l] is not None:
             res[f"z{l}"] = nm(be.host(zs[l]), zs64[l])
-    gws, gbs = [be.zeros(w.shape) for w in ws], [be.zeros(b.shape) for b in bs]
-    gx = be.zeros((R, dims[0])) if with_gx else None
-    wsb = be.bytes(api.size("cfd_ffn_stack_bwd_workspace_bytes", R, cdims, L))
+    gws, gbs = [be.out(w.shape) for w in ws], [be.out(b.shape) for b in bs]
+    gx = be.out((R, dims[0])) if with_gx else None
+    wsb = be.scratch(api.size("cfd_ffn_stack_bwd_workspace_bytes", R, cdims, L))
     api.call("cfd_ffn_stack_bwd", P(dx), P(dgy), arr(dws), arr(ys), arr(zs), arr(gws), arr(gbs), P(gx), P(wsb), R, cdims, L, code,
              int(act_last), be.stream)
     be.sync()
@@ -725,7 +745,7 @@ def check_rows_concat2(be, rows, ka, lda, kb, ldb, seed=73):
     rng = np.random.default_rng(seed)
     A = rng.standard_normal((rows, lda)).astype(np.float32)
     Bm = rng.standard_normal((rows, ldb)).astype(np.float32)
-    dA, dB, out = be.dev(A), be.dev(Bm), be.zeros((rows, ka + kb))
+    dA, dB, out = be.dev(A), be.dev(Bm), be.out((rows, ka + kb))
     api.call("cfd_rows_concat2", P(dA), lda, ka, P(dB), ldb, kb, P(out), rows, be.stream)
     be.sync()
     return {"differs": float(np.max(np.abs(be.host(out) - np.concatenate([A[:, :ka], Bm[:, :kb]], axis=1))))}
@@ -744,8 +764,8 @@ def check_mse_loss_strided_labels(be, rows, cols, ldl, seed=71):
     dg = [be.dev(v) for v in g]
     out = {}
     for name in ("ld", "contig"):
-        sums, scores, gp = be.zeros((4,)), be.zeros((4,)), be.zeros((rows, cols))
-        ws = be.bytes(api.size("cfd_loss_workspace_bytes", rows * cols))
+        sums, scores, gp = be.out((4,)), be.out((4,)), be.out((rows, cols))
+        ws = be.scratch(api.size("cfd_loss_workspace_bytes", rows * cols))
         if name == "ld":
             api.call("cfd_mse_loss_fwd_ld", P(dp), P(dbig), P(sums), P(scores), P(ws), rows, cols, ldl, be.stream)
             api.call("cfd_mse_loss_bwd_ld", P(dp), P(dbig), P(sums), *[P(v) for v in dg], P(gp), rows, cols, ldl, be.stream)
@@ -783,11 +803,11 @@ def check_linear_rowgemm6(be, M, K, N, act, in_act=None, seed=41, force=True):
         with tuned(be, gemm_b3=knob):
             dx, dw, db, dgy = be.dev(xin), be.dev(w), be.dev(b), be.dev(gy)
             dxpre = be.dev(xpre) if xpre is not None else None
-            y, pre = be.zeros((M, N)), be.zeros((M, N))
-            wsf = be.bytes(api.size("cfd_linear_fwd_workspace_bytes", M, K, N))
+            y, pre = be.out((M, N)), be.out((M, N))
+            wsf = be.scratch(api.size("cfd_linear_fwd_workspace_bytes", M, K, N))
             api.call("cfd_linear_fwd", P(dx), P(dw), P(db), P(y), P(pre), P(wsf), M, K, N, code[act], be.stream)
-            gx, gw, gb = be.zeros((M, K)), be.zeros((N, K)), be.zeros((N,))
-            wsb = be.bytes(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
+            gx, gw, gb = be.out((M, K)), be.out((N, K)), be.out((N,))
+            wsb = be.scratch(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
             api.call("cfd_linear_bwd_ex", P(dgy), P(dx), P(dw), P(y), P(pre), P(gx), P(gw), P(gb), P(wsb), M, K, N, code[act],
                      code[in_act] if in_act else 0, P(dxpre) if dxpre is not None else None, be.stream)
             be.sync()
@@ -814,11 +834,11 @@ def check_linear_chain_bwd(be, M, K, N, in_act, seed=37):
     w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
     gz = rng.standard_normal((M, N)).astype(np.float32)
     dx, dz, dw, dg = be.dev(x), be.dev(zin), be.dev(w), be.dev(gz)
-    gx1, gw1, gb1 = be.zeros((M, K)), be.zeros((N, K)), be.zeros((N,))
-    ws = be.bytes(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
+    gx1, gw1, gb1 = be.out((M, K)), be.out((N, K)), be.out((N,))
+    ws = be.scratch(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
     api.call("cfd_linear_bwd_ex", P(dg), P(dx), P(dw), None, None, P(gx1), P(gw1), P(gb1), P(ws), M, K, N, 0, code,
              P(dz) if code >= 3 else None, be.stream)
-    gx0, gw0, gb0, gx2 = be.zeros((M, K)), be.zeros((N, K)), be.zeros((N,)), be.zeros((M, K))
+    gx0, gw0, gb0, gx2 = be.out((M, K)), be.out((N, K)), be.out((N,)), be.out((M, K))
     api.call("cfd_linear_bwd", P(dg), P(dx), P(dw), None, None, P(gx0), P(gw0), P(gb0), P(ws), M, K, N, 0, be.stream)
     api.call("cfd_act_bwd", P(gx0), P(dx), P(dz), P(gx2), M * K, code, be.stream)
     be.sync()
@@ -848,11 +868,11 @@ def check_ffn_stacks(be, specs, seed=31):
                  cdims=(ctypes.c_int * (L + 1))(*dims))
         acted = [code != 0 and (l + 1 < L or act_last) for l in range(L)]
         for tag in ("one", "many"):  # outputs of the single-stack calls / of the joint call
-            d[tag] = dict(y=[be.zeros((R, dd)) for dd in dims[1:]],
-                          z=[be.zeros((R, dims[l + 1])) if (code >= 3 and acted[l]) else None for l in range(L)],
-                          gw=[be.zeros((dims[l + 1], dims[l])) for l in range(L)], gb=[be.zeros((dims[l + 1],)) for l in range(L)],
-                          gx=be.zeros((R, dims[0])) if with_gx else None,
-                          ws=be.bytes(api.size("cfd_ffn_stack_bwd_workspace_bytes", R, d["cdims"], L)))
+            d[tag] = dict(y=[be.out((R, dd)) for dd in dims[1:]],
+                          z=[be.out((R, dims[l + 1])) if (code >= 3 and acted[l]) else None for l in range(L)],
+                          gw=[be.out((dims[l + 1], dims[l])) for l in range(L)], gb=[be.out((dims[l + 1],)) for l in range(L)],
+                          gx=be.out((R, dims[0])) if with_gx else None,
+                          ws=be.scratch(api.size("cfd_ffn_stack_bwd_workspace_bytes", R, d["cdims"], L)))
         data.append(d)
     for d in data:
         o = d["one"]
@@ -894,17 +914,17 @@ def check_deeponet_inner(be, B, P_, Kq, HW, with_q, seed=23):
     g = rng.standard_normal((B, Kq)).astype(np.float32)
     dbr, dtr, dbi, du, dg = be.dev(br), be.dev(tr), be.dev(bias), be.dev(u), be.dev(g)
     dq = be.dev(q) if with_q else None
-    preds = be.zeros((B, Kq))
+    preds = be.out((B, Kq))
     api.call("cfd_deeponet_inner_fwd", P(dbr), P(dtr), P(dbi), P(du), P(dq), P(preds), B, P_, Kq, HW, be.stream)
     be.sync()
     resid = u[:, q] if with_q else u[:, :Kq]
     res = {"preds": nm(be.host(preds), br.astype(f64) @ tr.astype(f64).T + 0.37 + resid)}
-    p2 = be.zeros((B, Kq))
+    p2 = be.out((B, Kq))
     api.call("cfd_deeponet_inner_fwd", P(dbr), P(dtr), P(dbi), None, None, P(p2), B, P_, Kq, 0, be.stream)  # deeponet.py:205
     be.sync()
     res["preds_nores"] = nm(be.host(p2), br.astype(f64) @ tr.astype(f64).T + 0.37)
-    gbr, gtr, gbi = be.zeros((B, P_)), be.zeros((Kq, P_)), be.zeros((1,))
-    ws = be.bytes(api.size("cfd_deeponet_inner_bwd_workspace_bytes", B, P_, Kq))
+    gbr, gtr, gbi = be.out((B, P_)), be.out((Kq, P_)), be.out((1,))
+    ws = be.scratch(api.size("cfd_deeponet_inner_bwd_workspace_bytes", B, P_, Kq))
     api.call("cfd_deeponet_inner_bwd", P(dg), P(dbr), P(dtr), P(gbr), P(gtr), P(gbi), P(ws), B, P_, Kq, be.stream)
     be.sync()
     res["gbranch"] = nm(be.host(gbr), g.astype(f64) @ tr.astype(f64))
@@ -923,14 +943,14 @@ def check_conv2d(be, B, Ci, Co, H, W, ks, seed=31):
     b = rng.standard_normal((Co,)).astype(np.float32) * 0.2
     g = rng.standard_normal((B, Co, H, W)).astype(np.float32)
     dx, dw, db, dg = be.dev(x), be.dev(w), be.dev(b), be.dev(g)
-    out = be.zeros((B, Co, H, W))
+    out = be.out((B, Co, H, W))
     nws = api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks)
-    fws = be.bytes(nws) if nws else None
+    fws = be.scratch(nws) if nws else None
     api.call("cfd_conv2d_fwd", P(dx), P(dw), P(db), P(out), P(fws) if nws else None, B, Ci, Co, H, W, ks, be.stream)
     be.sync()
     res = {"out": nm(be.host(out), CO.conv2d(x.astype(f64), w.astype(f64), b.astype(f64)))}
-    ws = be.bytes(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
-    gin, gw, gb = be.zeros((B, Ci, H, W)), be.zeros((Co, Ci, ks, ks)), be.zeros((Co,))
+    ws = be.scratch(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Co, Ci, ks, ks)), be.out((Co,))
     api.call("cfd_conv2d_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, ks, be.stream)
     be.sync()
     rgx, rgw, rgb = CO.conv2d_bwd(g.astype(f64), x.astype(f64), w.astype(f64))
@@ -953,11 +973,11 @@ def check_conv2d_zeropad(be, B, Ci, Co, H, W, ks, seed=41):
     b = rng.standard_normal((Co,)).astype(np.float32) * 0.2
     g = rng.standard_normal((B, Co, H, W)).astype(np.float32)
     dx, dw, db, dg = be.dev(x), be.dev(w), be.dev(b), be.dev(g)
-    out = be.zeros((B, Co, H, W))
-    fws = be.bytes(api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    out = be.out((B, Co, H, W))
+    fws = be.scratch(api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks))
     api.call("cfd_conv2d_zeropad_fwd", P(dx), P(dw), P(db), P(out), P(fws), B, Ci, Co, H, W, ks, be.stream)
-    ws = be.bytes(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
-    gin, gw, gb = be.zeros((B, Ci, H, W)), be.zeros((Co, Ci, ks, ks)), be.zeros((Co,))
+    ws = be.scratch(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Co, Ci, ks, ks)), be.out((Co,))
     api.call("cfd_conv2d_zeropad_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, ks, be.stream)
     be.sync()
     pad4 = ((0, 0), (0, 0), (p, p), (p, p))
@@ -984,7 +1004,7 @@ def check_conv_prepared(be, layers, seed=37):
         for tr in (0, 1):
             n = api.size("cfd_conv2d_wfrag_bytes", Ci, Co, ks, tr)
             assert n > 0, (Ci, Co, ks, tr)
-            fr.append(be.bytes(n))
+            fr.append(be.scratch(n))
             items.append((P(w), P(fr[-1]), Ci, Co, ks, tr))
         data.append((x, w, b, g, fr))
     n = len(items)
@@ -996,20 +1016,21 @@ def check_conv_prepared(be, layers, seed=37):
     for (B, Ci, Co, H, W, ks), (x, w, b, g, fr) in zip(layers, data):
         outs = []
         for prepared in (False, True):
-            out = be.zeros((B, Co, H, W))
+            out = be.out((B, Co, H, W))
             nws = api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks)
             assert nws > 0
-            fws = be.bytes(nws)
+            fws = be.scratch(nws)
             slots = api.size("cfd_conv2d_fwd_stats_slots", B, Ci, Co, H, W, ks)
-            stats = be.zeros((Co, max(slots, 1), 4))
+            stats = be.out((Co, max(slots, 1), 4))
             api.call("cfd_conv2d_fwd_ex", P(x), P(w), P(b), P(out), P(fws), P(stats) if slots > 0 else None,
                      P(fr[0]) if prepared else None, B, Ci, Co, H, W, ks, be.stream)
-            ws = be.bytes(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
-            gin, gw, gb = be.zeros((B, Ci, H, W)), be.zeros((Co, Ci, ks, ks)), be.zeros((Co,))
+            ws = be.scratch(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
+            gin, gw, gb = be.out((B, Ci, H, W)), be.out((Co, Ci, ks, ks)), be.out((Co,))
             api.call("cfd_conv2d_bwd_ex", P(g), P(x), P(w), P(gin), P(gw), P(gb), P(ws), P(fr[1]) if prepared else None, B, Ci, Co, H, W,
                      ks, be.stream)
             be.sync()
-            outs.append([be.host(t).copy() for t in (out, stats, gin, gw, gb)])
+            # (a layer that emits no statistics gets NULL: its one-slot dummy is never written and is not compared)
+            outs.append([be.host(t).copy() for t in ((out, stats, gin, gw, gb) if slots > 0 else (out, gin, gw, gb))])
         for a, c in zip(*outs):
             bad += int(np.count_nonzero(a != c))
     return bad
@@ -1035,9 +1056,9 @@ def check_conv_bn_stats(be, B, Ci, Co, H, W, ks, relu=True, seed=36, offset=0.0,
     rm = (0.5 * rng.standard_normal(Co)).astype(np.float32)
     rv = (1 + rng.random(Co)).astype(np.float32)
     dx, dw, db, dga, dbe, drm, drv = be.dev(x), be.dev(w), be.dev(b), be.dev(gamma), be.dev(beta), be.dev(rm), be.dev(rv)
-    out, y, sm, sr = be.zeros((B, Co, H, W)), be.zeros((B, Co, H, W)), be.zeros((Co,)), be.zeros((Co,))
-    stats = be.zeros((Co, slots, 4))
-    ws = be.bytes(api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    out, y, sm, sr = be.out((B, Co, H, W)), be.out((B, Co, H, W)), be.out((Co,)), be.out((Co,))
+    stats = be.out((Co, slots, 4))
+    ws = be.scratch(api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks))
     api.call("cfd_conv2d_fwd_stats", P(dx), P(dw), P(db), P(out), P(ws), P(stats), B, Ci, Co, H, W, ks, be.stream)
     api.call("cfd_batchnorm_fwd_stats", P(out), P(dga), P(dbe), P(drm), P(drv), P(y), P(sm), P(sr), P(stats), slots, P(db), B, Co,
              H * W, 1e-5, 0.1, int(relu), be.stream)
@@ -1058,15 +1079,15 @@ def check_batchnorm(be, B, C, H, W, training, relu, seed=32):
     rv = (1 + rng.random(C)).astype(np.float32)
     gy = rng.standard_normal((B, C, H, W)).astype(np.float32)
     dx, dga, dbe, drm, drv, dgy = be.dev(x), be.dev(gamma), be.dev(beta), be.dev(rm), be.dev(rv), be.dev(gy)
-    y, sm, sr = be.zeros((B, C, H, W)), be.zeros((C,)), be.zeros((C,))
-    ws = be.bytes(api.size("cfd_batchnorm_workspace_bytes", C))
+    y, sm, sr = be.out((B, C, H, W)), be.out((C,)), be.out((C,))
+    ws = be.scratch(api.size("cfd_batchnorm_workspace_bytes", C))
     api.call("cfd_batchnorm_fwd", P(dx), P(dga), P(dbe), P(drm), P(drv), P(y), P(sm), P(sr), P(ws), B, C, H * W, 1e-5, 0.1,
              int(training), int(relu), be.stream)
     be.sync()
     ry, cache, nrm, nrv = CO.batchnorm(x.astype(f64), gamma.astype(f64), beta.astype(f64), rm.astype(f64), rv.astype(f64),
                                        training, relu=relu)
     res = {"y": nm(be.host(y), ry), "run_mean": nm(be.host(drm), nrm), "run_var": nm(be.host(drv), nrv)}
-    gx, gga, gbe = be.zeros((B, C, H, W)), be.zeros((C,)), be.zeros((C,))
+    gx, gga, gbe = be.out((B, C, H, W)), be.out((C,)), be.out((C,))
     api.call("cfd_batchnorm_bwd", P(dgy), P(dx), P(dga), P(dbe), P(sm), P(sr), P(gx), P(gga), P(gbe), P(ws), B, C, H * W,
              int(training), int(relu), be.stream)
     be.sync()
@@ -1087,10 +1108,10 @@ def check_convt(be, B, Ci, Co, H, W, seed=34, x=None, rng=None):
     b = rng.standard_normal((Co,)).astype(np.float32) * 0.1
     g = rng.standard_normal((B, Co, 2 * H, 2 * W)).astype(np.float32)
     dw, db, dg = be.dev(w), be.dev(b), be.dev(g)
-    out = be.zeros((B, Co, 2 * H, 2 * W))
+    out = be.out((B, Co, 2 * H, 2 * W))
     api.call("cfd_convt2_fwd", P(dx), P(dw), P(db), P(out), B, Ci, Co, H, W, be.stream)
-    ws = be.bytes(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
-    gin, gw, gb = be.zeros((B, Ci, H, W)), be.zeros((Ci, Co, 2, 2)), be.zeros((Co,))
+    ws = be.scratch(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
+    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Ci, Co, 2, 2)), be.out((Co,))
     api.call("cfd_convt2_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, be.stream)
     be.sync()
     res = {"convt": nm(be.host(out), CO.convt2(x.astype(f64), w.astype(f64), b.astype(f64)))}
@@ -1106,17 +1127,17 @@ def check_pool_convt_resid(be, B, Ci, Co, H, W, seed=33):
     x = np.maximum(rng.standard_normal((B, Ci, H, W)), 0).astype(np.float32)  # ReLU-like input: ties at zero
     dx = be.dev(x)
     Ho, Wo = H // 2, W // 2
-    y = be.zeros((B, Ci, Ho, Wo))
+    y = be.out((B, Ci, Ho, Wo))
     api.call("cfd_maxpool2_fwd", P(dx), P(y), B * Ci, H, W, be.stream)
     gy = rng.standard_normal((B, Ci, Ho, Wo)).astype(np.float32)
-    dgy, gx = be.dev(gy), be.zeros((B, Ci, H, W))
+    dgy, gx = be.dev(gy), be.out((B, Ci, H, W))
     api.call("cfd_maxpool2_bwd", P(dx), P(dgy), P(gx), B * Ci, H, W, be.stream)
     be.sync()
     res = {"pool": float(np.abs(be.host(y) - CO.maxpool2(x)).max()),
            "pool_bwd": float(np.abs(be.host(gx) - CO.maxpool2_bwd(x, gy)).max())}
     # the same with the skip connection's gradient summed in: a channel slice (first Ci of Ci + 3 channels) of a larger tensor
     gcat = rng.standard_normal((B, Ci + 3, H, W)).astype(np.float32)
-    dgcat, gx2 = be.dev(gcat), be.zeros((B, Ci, H, W))
+    dgcat, gx2 = be.dev(gcat), be.out((B, Ci, H, W))
     api.call("cfd_maxpool2_bwd_add", P(dx), P(dgy), P(dgcat), (Ci + 3) * H * W, P(gx2), B, Ci, H, W, be.stream)
     be.sync()
     res["pool_bwd_add"] = float(np.abs(be.host(gx2) - (be.host(gx) + gcat[:, :Ci])).max())  # one fp32 add: exact
@@ -1124,7 +1145,7 @@ def check_pool_convt_resid(be, B, Ci, Co, H, W, seed=33):
     C2 = min(2, Ci)
     mask = (rng.random((B, H * W)) > 0.2).astype(np.float32)
     xs = rng.standard_normal((B, C2, H * W)).astype(np.float32)
-    dxs, dmask, o2 = be.dev(xs), be.dev(mask), be.zeros((B, C2, H * W))
+    dxs, dmask, o2 = be.dev(xs), be.dev(mask), be.out((B, C2, H * W))
     api.call("cfd_residual_mask", P(dxs), P(dx), P(dmask), P(o2), B, C2, Ci, H * W, be.stream)
     be.sync()
     res["resid"] = nm(be.host(o2), (xs + x.reshape(B, Ci, -1)[:, :C2]) * mask[:, None])
@@ -1140,7 +1161,7 @@ def check_upsample_bilinear(be, B, C, H, W, seed=35):
     x = rng.standard_normal((B, C, H, W)).astype(np.float32)
     g = rng.standard_normal((B, C, 2 * H, 2 * W)).astype(np.float32)
     dx, dg = be.dev(x), be.dev(g)
-    y, gx = be.zeros((B, C, 2 * H, 2 * W)), be.zeros((B, C, H, W))
+    y, gx = be.out((B, C, 2 * H, 2 * W)), be.out((B, C, H, W))
     api.call("cfd_upsample2_bilinear_fwd", P(dx), P(y), B * C, H, W, be.stream)
     api.call("cfd_upsample2_bilinear_bwd", P(dg), P(gx), B * C, H, W, be.stream)
     be.sync()
@@ -1161,7 +1182,7 @@ def check_normact(be, S, shape, act, seed=41):
     g = rng.standard_normal((S,) + shape).astype(np.float32)
     L = int(np.prod(shape))
     dx, dg = be.dev(x), be.dev(g)
-    y, stats, gx = be.zeros((S,) + shape), be.zeros((S, 2)), be.zeros((S,) + shape)
+    y, stats, gx = be.out((S,) + shape), be.out((S, 2)), be.out((S,) + shape)
     api.call("cfd_normact_fwd", P(dx), P(y), P(stats), S, L, code, be.stream)
     api.call("cfd_normact_bwd", P(dx), P(dg), P(stats), P(gx), S, L, code, be.stream)
     be.sync()
@@ -1175,7 +1196,7 @@ def check_bcast_rowdot(be, B, K, P_, seed=42):
     ft, fxy = rng.standard_normal((B, P_)).astype(np.float32), rng.standard_normal((K, P_)).astype(np.float32)
     g3 = rng.standard_normal((B, K, P_)).astype(np.float32)
     dft, dfxy, dg3 = be.dev(ft), be.dev(fxy), be.dev(g3)
-    out, gft, gfxy = be.zeros((B, K, P_)), be.zeros((B, P_)), be.zeros((K, P_))
+    out, gft, gfxy = be.out((B, K, P_)), be.out((B, P_)), be.out((K, P_))
     api.call("cfd_bcast_add_fwd", P(dft), P(dfxy), P(out), B, K, P_, be.stream)
     api.call("cfd_bcast_add_bwd", P(dg3), P(gft), P(gfxy), B, K, P_, be.stream)
     be.sync()
@@ -1184,8 +1205,8 @@ def check_bcast_rowdot(be, B, K, P_, seed=42):
     br, tr = rng.standard_normal((B, P_)).astype(np.float32), rng.standard_normal((B, K, P_)).astype(np.float32)
     bias, g2 = np.array([0.21], np.float32), rng.standard_normal((B, K)).astype(np.float32)
     dbr, dtr, dbi, dg2 = be.dev(br), be.dev(tr), be.dev(bias), be.dev(g2)
-    preds, gbr, gtr, gbi = be.zeros((B, K)), be.zeros((B, P_)), be.zeros((B, K, P_)), be.zeros((1,))
-    ws = be.bytes(api.size("cfd_rowdot_bwd_workspace_bytes"))
+    preds, gbr, gtr, gbi = be.out((B, K)), be.out((B, P_)), be.out((B, K, P_)), be.out((1,))
+    ws = be.scratch(api.size("cfd_rowdot_bwd_workspace_bytes"))
     api.call("cfd_rowdot_fwd", P(dbr), P(dtr), P(dbi), P(preds), B, K, P_, be.stream)
     api.call("cfd_rowdot_bwd", P(dg2), P(dbr), P(dtr), P(gbr), P(gtr), P(gbi), P(ws), B, K, P_, be.stream)
     be.sync()
@@ -1205,7 +1226,7 @@ def check_act(be, n, act, seed=43):
     x = (rng.standard_normal(n) * 1.5).astype(np.float32)
     g = rng.standard_normal(n).astype(np.float32)
     dx, dg = be.dev(x), be.dev(g)
-    y, gx = be.zeros((n,)), be.zeros((n,))
+    y, gx = be.out((n,)), be.out((n,))
     api.call("cfd_act_fwd", P(dx), P(y), n, code, be.stream)
     api.call("cfd_act_bwd", P(dg), P(y), P(dx), P(gx), n, code, be.stream)
     be.sync()
@@ -1221,7 +1242,7 @@ def check_dropout_gelu(be, n, p, seed=5):
     x = (2.5 * rng.standard_normal(n)).astype(np.float32)
     g = rng.standard_normal(n).astype(np.float32)
     dx, dg = be.dev(x), be.dev(g)
-    y1, gx1, d, y2, t, gx2 = (be.zeros((n,)) for _ in range(6))
+    y1, gx1, d, y2, t, gx2 = (be.out((n,)) for _ in range(6))
     api.call("cfd_dropout_gelu_fwd", P(dx), P(y1), n, p, 1234, be.stream)
     api.call("cfd_dropout_gelu_bwd", P(dx), P(dg), P(gx1), n, p, 1234, be.stream)
     api.call("cfd_dropout", P(dx), P(d), n, p, 1234, be.stream)
@@ -1251,7 +1272,7 @@ def check_dropout_step(be, n, p, base, step, seed=7):
     g = rng.standard_normal(n).astype(np.float32)
     dx, dg = be.dev(x), be.dev(g)
     dstep = be.dev(np.array([step], dtype=np.int64))
-    y1, gx1, y2, gx2 = (be.zeros((n,)) for _ in range(4))
+    y1, gx1, y2, gx2 = (be.out((n,)) for _ in range(4))
     host_seed = mix64(base + step) & 0xFFFFFFFFFFFF
     api.call("cfd_dropout_gelu_fwd_step", P(dx), P(y1), n, p, base, P(dstep), be.stream)
     api.call("cfd_dropout_gelu_bwd_step", P(dx), P(dg), P(gx1), n, p, base, P(dstep), be.stream)
@@ -1273,22 +1294,22 @@ def check_loss_scores_bwd(be, seed=6):
         n = float(rng.integers(10, 100000))
         sums = np.array([rng.random() * n, rng.random() * n, (0.5 + rng.random()) * n, n], np.float32)
         g = rng.standard_normal(4).astype(np.float32)
-        ds, scores = be.dev(sums), be.zeros((4,))
+        ds, scores = be.dev(sums), be.out((4,))
         api.call("cfd_loss_scores", P(ds), P(scores), be.stream)
         s0, s1, s2, nn = (float(v) for v in sums)
         ref = np.array([s0 / nn, np.sqrt(s0 / nn), s1 / nn, s0 / s2])
         be.sync()
-        worst = max(worst, float(np.abs(be.host(scores) - ref).max() / np.abs(ref).max()))
+        worst = nan_max(worst, float(np.abs(be.host(scores) - ref).max() / np.abs(ref).max()))
         jac = np.array([[1 / nn, 0, 0], [0.5 / np.sqrt(s0 / nn) / nn, 0, 0], [0, 1 / nn, 0], [1 / s2, 0, -s0 / s2 ** 2]])  # d score_i / d sums_j
         for pick in ([0], [1], [2], [3], [0, 1, 2, 3]):
             gd = [be.dev(g[i:i + 1]) if i in pick else None for i in range(4)]
-            out = be.zeros((4,))
+            out = be.out((4,))
             api.call("cfd_loss_scores_bwd", P(ds), *[P(t) if t is not None else None for t in gd], P(out), be.stream)
             be.sync()
             want = sum(g[i] * jac[i] for i in pick)
             got = be.host(out)
             assert got[3] == 0.0
-            worst = max(worst, float(np.abs(got[:3] - want).max() / max(np.abs(want).max(), 1e-30)))
+            worst = nan_max(worst, float(np.abs(got[:3] - want).max() / max(np.abs(want).max(), 1e-30)))
     return worst
 
 
@@ -1303,6 +1324,8 @@ def check_adam_multi(be, sizes=(7, 1025, 300, 1), steps=3, seed=8, shift_odd=Fal
     sh = [1 if (shift_odd and t % 2) else 0 for t in range(len(sizes))]
     pad = lambda a, s_: np.concatenate([np.zeros(s_, np.float32), a])
     p0 = [rng.standard_normal(n).astype(np.float32) for n in sizes]
+    # cfdbench_amd.h, cfd_adam_flat / cfd_adam_multi: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them
+    # before step 1" -- carried-in buffers, so zeros() here
     pa, ma, va = ([be.dev(pad(t, s_)) for t, s_ in zip(p0, sh)], [be.zeros((n + s_,)) for n, s_ in zip(sizes, sh)],
                   [be.zeros((n + s_,)) for n, s_ in zip(sizes, sh)])
     pb, mb, vb = [be.dev(t) for t in p0], [be.zeros((n,)) for n in sizes], [be.zeros((n,)) for n in sizes]
@@ -1317,7 +1340,7 @@ def check_adam_multi(be, sizes=(7, 1025, 300, 1), steps=3, seed=8, shift_odd=Fal
         for t in range(len(sizes)):
             api.call("cfd_adam_flat", P(pb[t]), P(g[t]), P(mb[t]), P(vb[t]), sizes[t], 2e-3, 0.9, 0.999, 1e-8, 0.01, k, 1.0, be.stream)
         be.sync()
-    return max(float(np.abs(be.host(a)[s_:] - be.host(b)).max() / np.abs(be.host(b)).max()) for a, b, s_ in zip(pa, pb, sh))
+    return nan_max(*[float(np.abs(be.host(a)[s_:] - be.host(b)).max() / np.abs(be.host(b)).max()) for a, b, s_ in zip(pa, pb, sh)])
 
 
 def check_adam_flat_unaligned(be, n=1003, seed=10):
@@ -1373,16 +1396,16 @@ def check_convt_strided(be, B, Ci, Co, H, W, C2=3, seed=40):
     gwide = rng.standard_normal((B, C2 + Co, 2 * H, 2 * W)).astype(np.float32)
     dx, dw, db = be.dev(x), be.dev(w), be.dev(b)
     plane = 4 * H * W
-    out = be.zeros((B, Co, 2 * H, 2 * W))
+    out = be.out((B, Co, 2 * H, 2 * W))
     api.call("cfd_convt2_fwd", P(dx), P(dw), P(db), P(out), B, Ci, Co, H, W, be.stream)
     wide = be.dev(np.full((B, C2 + Co, 2 * H, 2 * W), 7.0, np.float32))
     api.call("cfd_convt2_fwd_ex", P(dx), P(dw), P(db), P(wide) + 4 * C2 * plane, (C2 + Co) * plane, B, Ci, Co, H, W, be.stream)
-    ws = be.bytes(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
+    ws = be.scratch(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
     dg = be.dev(np.ascontiguousarray(gwide[:, C2:]))
-    gin, gw, gb = be.zeros((B, Ci, H, W)), be.zeros((Ci, Co, 2, 2)), be.zeros((Co,))
+    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Ci, Co, 2, 2)), be.out((Co,))
     api.call("cfd_convt2_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, be.stream)
     dgw = be.dev(gwide)
-    gin2, gw2, gb2 = be.zeros((B, Ci, H, W)), be.zeros((Ci, Co, 2, 2)), be.zeros((Co,))
+    gin2, gw2, gb2 = be.out((B, Ci, H, W)), be.out((Ci, Co, 2, 2)), be.out((Co,))
     api.call("cfd_convt2_bwd_ex", P(dgw) + 4 * C2 * plane, (C2 + Co) * plane, P(dx), P(dw), P(gin2), P(gw2), P(gb2), P(ws), B, Ci, Co, H, W,
              be.stream)
     be.sync()
@@ -1391,3 +1414,338 @@ def check_convt_strided(be, B, Ci, Co, H, W, C2=3, seed=40):
     for a, c in ((gin, gin2), (gw, gw2), (gb, gb2)):
         bad += int(np.count_nonzero(be.host(a) != be.host(c)))
     return bad
+
+
+# ---- a second call on dirty buffers ----------------------------------------------------------------------------------
+# The engine and FnoRollout size outputs and a workspace once and reuse them for every later step and shape.  The cases below
+# take their outputs and workspaces from an Arena, so that the same code runs on fresh poisoned buffers or on the buffers an
+# earlier, LARGER call left behind (stale plausible values instead of NaN); the kernels use no atomics, so the two runs of the
+# smaller shape must agree bit for bit.
+class Arena:
+    """Source of a case's outputs (`out`) and workspaces (`scratch`): fresh hostile buffers of the backend, or -- with `reuse` =
+    the Arena of an earlier run of the same case -- that run's buffers in the order they were asked for, the leading elements of
+    each viewed at the new shape (same base pointer).  `share` names the kinds that are reused; the others stay fresh."""
+
+    def __init__(self, be, reuse=None, share=("out", "scratch")):
+        self.be, self.reuse, self.share = be, reuse, share
+        self.log = {"out": [], "scratch": []}
+        self.at = {"out": 0, "scratch": 0}
+
+    def _old(self, kind):
+        buf = self.reuse.log[kind][self.at[kind]]
+        self.at[kind] += 1
+        return buf
+
+    def out(self, shape, dtype=np.float32):
+        if self.reuse is not None and "out" in self.share:
+            flat, n = self._old("out").reshape(-1), int(np.prod(shape))
+            assert flat.shape[0] >= n and self.be.host(flat[:1]).dtype == np.dtype(dtype), (shape, dtype)
+            buf = flat[:n].reshape(shape)
+        else:
+            buf = self.be.out(shape, dtype)
+        self.log["out"].append(buf)
+        return buf
+
+    def scratch(self, n):
+        n = max(int(n), 1)
+        if self.reuse is not None and "scratch" in self.share:
+            old = self._old("scratch")
+            assert old.shape[0] >= n, (old.shape, n)
+            buf = old[:n]
+        else:
+            buf = self.be.scratch(n)
+        self.log["scratch"].append(buf)
+        return buf
+
+
+def words_that_differ(a, b):
+    """32-bit words in which two host arrays differ (bit patterns, so a NaN equals only the same NaN) plus the non-finite values
+    of `b`: 0 iff `a` is bitwise `b` and `b` is finite."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    fin = np.isfinite(b) if b.dtype.kind in "fc" else np.ones(b.shape, bool)
+    return int(np.count_nonzero(a.reshape(-1).view(np.uint32) != b.reshape(-1).view(np.uint32))) + int(np.count_nonzero(~fin))
+
+
+def check_dirty_reuse(be, case, big, small):
+    """`case` at shape `big`, then at the smaller shape `small` into the SAME outputs and workspaces (sized for `big`), against
+    `small` alone on fresh poisoned buffers.  Returns the number of differing words per result (all zero)."""
+    fresh = case(be, Arena(be), **small)
+    first = Arena(be)
+    case(be, first, **big)
+    again = case(be, Arena(be, reuse=first), **small)
+    assert fresh.keys() == again.keys()
+    return {k: words_that_differ(again[k], fresh[k]) for k in fresh}
+
+
+def _fno_setup(be, B, C, L, H, W, m1, m2, p, seed):
+    params = synth.make_fno_params(seed, C, L, m1, m2, p, spectral_gain=4.0)
+    batch = synth.make_batch(seed + 1, B, H, W, p, border_mask=True)
+    return params, {k: be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label")}
+
+
+def fno_ws_bytes(be, B, C, L, H=64, W=64, m1=12, m2=12, p=5, training=1):
+    plan = be.api.plan_create(H, W, m1, m2)
+    try:
+        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
+        return be.api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), training)
+    finally:
+        be.api.plan_destroy(plan)
+
+
+def case_fno(be, ar, B, C, L, H=64, W=64, m1=12, m2=12, p=5, seed=81, ws_min=0):
+    """cfd_fno_forward (training workspace) + cfd_loss_coef + cfd_fno_backward, then cfd_fno_forward on the inference workspace.
+    ws_min: allocate at least that many workspace bytes (one workspace sized for several routes)."""
+    api, P = be.api, be.ptr
+    params, d = _fno_setup(be, B, C, L, H, W, m1, m2, p, seed)
+    plan = api.plan_create(H, W, m1, m2)
+    try:
+        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
+        sh = ctypes.byref(shape)
+        pd = {k: be.dev(v) for k, v in params.items()}
+        ws = ar.scratch(max(api.size("cfd_fno_workspace_bytes", plan, sh, 1), ws_min))
+        ws0 = ar.scratch(max(api.size("cfd_fno_workspace_bytes", plan, sh, 0), ws_min))
+        preds, sums, coef, preds0 = ar.out((B, 2, H, W)), ar.out((4,)), ar.out((2,)), ar.out((B, 2, H, W))
+        gd = {k: ar.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
+        ps, gs = make_param_struct(be, pd, L), make_param_struct(be, gd, L)
+        pr, gr = ctypes.byref(ps), ctypes.byref(gs)
+        api.call("cfd_fno_forward", plan, sh, pr, P(d["inputs"]), P(d["case_params"]), P(d["mask"]), P(d["label"]), P(preds), P(sums),
+                 P(ws), 1, be.stream)
+        api.call("cfd_loss_coef", P(sums), P(coef), 1, 1.0, be.stream)
+        api.call("cfd_fno_backward", plan, sh, pr, gr, P(d["inputs"]), P(d["case_params"]), P(d["mask"]), P(d["label"]), P(preds), None,
+                 P(coef), P(ws), be.stream)
+        api.call("cfd_fno_forward", plan, sh, pr, P(d["inputs"]), P(d["case_params"]), P(d["mask"]), None, P(preds0), None, P(ws0), 0,
+                 be.stream)
+        be.sync()
+        res = {"preds": be.host(preds), "sums": be.host(sums), "coef": be.host(coef), "preds_infer": be.host(preds0)}
+        res.update({"g:" + k: be.host(v) for k, v in gd.items()})
+        return res
+    finally:
+        api.plan_destroy(plan)
+
+
+def case_fno_train_step(be, ar, B, C, L, H=64, W=64, m1=12, m2=12, p=5, flags=0, which="nmse", steps=2, seed=83, ws_min=0):
+    """The fused training step (cfd_fno_forward_train_f / cfd_fno_backward_phase_f / cfd_fno_adam_step) for `steps` steps: predictions,
+    loss sums, the last gradient and the parameters after the steps.  Parameters, gradient and moments are the caller's state (fresh
+    per run); predictions, sums, coef and the workspace come from the arena."""
+    api, P = be.api, be.ptr
+    wid = {"mse": 0, "nmse": 1, "mae": 2}[which]
+    params, d = _fno_setup(be, B, C, L, H, W, m1, m2, p, seed)
+    names = ["fc0.weight", "fc0.bias"] + [f"blocks.{l}.{t}" for l in range(L) for t in ("conv0.weights1", "conv0.weights2", "w0.weight", "w0.bias")] \
+        + ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
+    layout, off = {}, 0
+    for k in names:
+        n = params[k].size * (2 if np.iscomplexobj(params[k]) else 1)
+        layout[k] = (off, n)
+        off += (n + 3) // 4 * 4
+    flat0 = np.zeros(off, np.float32)
+    for k in names:
+        v = params[k]
+        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
+    plan = api.plan_create(H, W, m1, m2)
+    try:
+        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
+        sh = ctypes.byref(shape)
+        flat, grad = be.dev(flat0), flat_grad_buffer(be, layout, off)
+        # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
+        m, v = be.zeros((off,)), be.zeros((off,))
+        ps, gs = _flat_struct(be, flat, layout, L), _flat_struct(be, grad, layout, L)
+        pr, gr = ctypes.byref(ps), ctypes.byref(gs)
+        ws = ar.scratch(max(api.size("cfd_fno_workspace_bytes", plan, sh, 1), ws_min))
+        preds, sums, coef = ar.out((B, 2, H, W)), ar.out((4,)), ar.out((2,))
+        a = (P(d["inputs"]), P(d["case_params"]), P(d["mask"]))
+        for step in range(1, steps + 1):
+            api.call("cfd_fno_forward_train_f", plan, sh, pr, gr, *a, P(d["label"]), P(preds), P(sums), P(coef), P(ws), wid, 1.0, 0, flags,
+                     be.stream)
+            for phase in range(1, L + 2):
+                api.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *a, P(d["label"]), P(preds), None, P(coef), P(sums), P(ws), phase, wid,
+                         0, flags, be.stream)
+            api.call("cfd_fno_adam_step", plan, sh, pr, gr, *a, P(sums), P(ws), P(flat), P(grad), P(m), P(v), off, 1e-3, 0.9, 0.999, 1e-8,
+                     0.0, step, 1.0, wid, 0, flags, be.stream)
+        be.sync()
+        return {"preds": be.host(preds), "sums": be.host(sums), "grad": be.host(grad), "params": be.host(flat)}
+    finally:
+        api.plan_destroy(plan)
+
+
+def check_workspace_across_routes(be, case=case_fno, **extra):
+    """ONE workspace, sized as the largest of the three, serves the default route (hidden 20, 12 x 12 modes), then the wide route
+    (hidden 64), then the many-modes route (24 x 24 modes): each must equal its run on a fresh workspace bit for bit."""
+    cfgs = {"default": dict(B=1, C=20, L=1), "wide": dict(B=1, C=64, L=1), "modes": dict(B=1, C=6, L=1, m1=24, m2=24)}
+    need = max(max(fno_ws_bytes(be, **c, training=t) for t in (0, 1)) for c in cfgs.values())
+    res, prev = {}, None
+    for name, c in cfgs.items():
+        fresh = case(be, Arena(be), **c, **extra)
+        ar = Arena(be, reuse=prev, share=("scratch",))
+        got = case(be, ar, **c, ws_min=need, **extra)
+        prev = ar
+        res.update({f"{name}.{k}": words_that_differ(got[k], fresh[k]) for k in fresh})
+    return res
+
+
+def case_spectral(be, ar, B, Cin, Cout, H=64, W=64, m1=12, m2=12, seed=85):
+    """cfd_spectral_conv2d_fwd / _bwd."""
+    api, P = be.api, be.ptr
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((B, Cin, H, W)).astype(np.float32)
+    gy = rng.standard_normal((B, Cout, H, W)).astype(np.float32)
+    w1 = (rng.random((Cin, Cout, m1, m2)) + 1j * rng.random((Cin, Cout, m1, m2))).astype(np.complex64)
+    w2 = (rng.random((Cin, Cout, m1, m2)) + 1j * rng.random((Cin, Cout, m1, m2))).astype(np.complex64)
+    plan = api.plan_create(H, W, m1, m2)
+    try:
+        dx, dgy, dw1, dw2 = be.dev(x), be.dev(gy), be.dev(w1), be.dev(w2)
+        xh, z = ar.out((B, Cin, 2 * m1, m2), np.complex64), ar.out((B, Cout, 2 * m1, m2), np.complex64)
+        y, gx = ar.out((B, Cout, H, W)), ar.out((B, Cin, H, W))
+        gw1, gw2 = ar.out((Cin, Cout, m1, m2), np.complex64), ar.out((Cin, Cout, m1, m2), np.complex64)
+        ws = ar.scratch(api.size("cfd_spectral_conv2d_bwd_workspace_bytes", plan, B, Cin, Cout))
+        api.call("cfd_spectral_conv2d_fwd", plan, P(dx), P(dw1), P(dw2), P(y), P(xh), P(z), B, Cin, Cout, be.stream)
+        api.call("cfd_spectral_conv2d_bwd", plan, P(dgy), P(xh), P(dw1), P(dw2), P(gx), P(gw1), P(gw2), P(ws), B, Cin, Cout, be.stream)
+        be.sync()
+        return {"xh": be.host(xh), "y": be.host(y), "gx": be.host(gx), "gw1": be.host(gw1), "gw2": be.host(gw2)}
+    finally:
+        api.plan_destroy(plan)
+
+
+def case_block(be, ar, B, C, H=64, W=64, m1=12, m2=12, seed=86):
+    """cfd_fno_block_fwd (GELU on load) / cfd_fno_block_bwd_input (with gelu')."""
+    api, P = be.api, be.ptr
+    rng = np.random.default_rng(seed)
+    a = rng.standard_normal((B, C, H, W)).astype(np.float32)
+    g = rng.standard_normal((B, C, H, W)).astype(np.float32)
+    z = (rng.standard_normal((B, C, 2 * m1, m2)) + 1j * rng.standard_normal((B, C, 2 * m1, m2))).astype(np.complex64)
+    w0 = rng.standard_normal((C, C)).astype(np.float32)
+    b0 = rng.standard_normal((C,)).astype(np.float32)
+    plan = api.plan_create(H, W, m1, m2)
+    try:
+        da, dg, dz, dw, db = be.dev(a), be.dev(g), be.dev(z), be.dev(w0), be.dev(b0)
+        out, gin = ar.out((B, C, H, W)), ar.out((B, C, H, W))
+        api.call("cfd_fno_block_fwd", plan, P(da), P(dz), P(dw), P(db), P(out), B, C, C, 1, be.stream)
+        api.call("cfd_fno_block_bwd_input", plan, P(dg), P(dz), P(dw), P(da), P(gin), B, C, C, be.stream)
+        be.sync()
+        return {"out": be.host(out), "gin": be.host(gin)}
+    finally:
+        api.plan_destroy(plan)
+
+
+def case_conv(be, ar, B, Ci, Co, H, W, ks, seed=87):
+    """cfd_conv2d_fwd_ex (with the BatchNorm records where the layer emits them: the _stats form) / cfd_conv2d_bwd_ex, own fragments."""
+    api, P = be.api, be.ptr
+    rng = np.random.default_rng(seed)
+    x = be.dev(rng.standard_normal((B, Ci, H, W)).astype(np.float32))
+    w = be.dev((rng.standard_normal((Co, Ci, ks, ks)) / np.sqrt(Ci * ks * ks)).astype(np.float32))
+    b = be.dev(rng.standard_normal((Co,)).astype(np.float32) * 0.2)
+    g = be.dev(rng.standard_normal((B, Co, H, W)).astype(np.float32))
+    slots = api.size("cfd_conv2d_fwd_stats_slots", B, Ci, Co, H, W, ks)
+    out, stats = ar.out((B, Co, H, W)), ar.out((Co, max(slots, 1), 4))  # (slots = 0: the layer emits none and gets NULL)
+    fws = ar.scratch(api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    ws = ar.scratch(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
+    gin, gw, gb = ar.out((B, Ci, H, W)), ar.out((Co, Ci, ks, ks)), ar.out((Co,))
+    api.call("cfd_conv2d_fwd_ex", P(x), P(w), P(b), P(out), P(fws), P(stats) if slots > 0 else None, None, B, Ci, Co, H, W, ks, be.stream)
+    api.call("cfd_conv2d_bwd_ex", P(g), P(x), P(w), P(gin), P(gw), P(gb), P(ws), None, B, Ci, Co, H, W, ks, be.stream)
+    be.sync()
+    res = {"out": be.host(out), "gin": be.host(gin), "gw": be.host(gw), "gb": be.host(gb)}
+    if slots > 0:
+        res["stats"] = be.host(stats)
+    return res
+
+
+def case_convt(be, ar, B, Ci, Co, H, W, seed=88):
+    """cfd_convt2_fwd / cfd_convt2_bwd."""
+    api, P = be.api, be.ptr
+    rng = np.random.default_rng(seed)
+    x = be.dev(rng.standard_normal((B, Ci, H, W)).astype(np.float32))
+    w = be.dev((rng.standard_normal((Ci, Co, 2, 2)) / np.sqrt(Ci)).astype(np.float32))
+    b = be.dev(rng.standard_normal((Co,)).astype(np.float32) * 0.1)
+    g = be.dev(rng.standard_normal((B, Co, 2 * H, 2 * W)).astype(np.float32))
+    out = ar.out((B, Co, 2 * H, 2 * W))
+    ws = ar.scratch(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
+    gin, gw, gb = ar.out((B, Ci, H, W)), ar.out((Ci, Co, 2, 2)), ar.out((Co,))
+    api.call("cfd_convt2_fwd", P(x), P(w), P(b), P(out), B, Ci, Co, H, W, be.stream)
+    api.call("cfd_convt2_bwd", P(g), P(x), P(w), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, be.stream)
+    be.sync()
+    return {"out": be.host(out), "gin": be.host(gin), "gw": be.host(gw), "gb": be.host(gb)}
+
+
+def case_ffn_stack(be, ar, R, dims, act="gelu", seed=89):
+    """cfd_ffn_stack_fwd / _bwd."""
+    api, P = be.api, be.ptr
+    code = {"none": 0, "relu": 1, "tanh": 2, "gelu": 3, "swish": 4}[act]
+    rng = np.random.default_rng(seed)
+    L = len(dims) - 1
+    dx = be.dev(rng.standard_normal((R, dims[0])).astype(np.float32))
+    dws = [be.dev((rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32)) for l in range(L)]
+    dbs = [be.dev((0.3 * rng.standard_normal((dims[l + 1],))).astype(np.float32)) for l in range(L)]
+    dgy = be.dev(rng.standard_normal((R, dims[L])).astype(np.float32))
+    ys = [ar.out((R, d)) for d in dims[1:]]
+    zs = [ar.out((R, dims[l + 1])) if (code >= 3 and l + 1 < L) else None for l in range(L)]
+    gws, gbs, gx = [ar.out((dims[l + 1], dims[l])) for l in range(L)], [ar.out((dims[l + 1],)) for l in range(L)], ar.out((R, dims[0]))
+    arr = lambda ts: (ctypes.c_void_p * len(ts))(*[P(t) for t in ts])  # noqa: E731
+    cdims = (ctypes.c_int * (L + 1))(*dims)
+    wsb = ar.scratch(api.size("cfd_ffn_stack_bwd_workspace_bytes", R, cdims, L))
+    api.call("cfd_ffn_stack_fwd", P(dx), arr(dws), arr(dbs), arr(ys), arr(zs), R, cdims, L, code, 0, be.stream)
+    api.call("cfd_ffn_stack_bwd", P(dx), P(dgy), arr(dws), arr(ys), arr(zs), arr(gws), arr(gbs), P(gx), P(wsb), R, cdims, L, code, 0, be.stream)
+    be.sync()
+    res = {"gx": be.host(gx)}
+    for l in range(L):
+        res[f"y{l}"], res[f"gw{l}"], res[f"gb{l}"] = be.host(ys[l]), be.host(gws[l]), be.host(gbs[l])
+    return res
+
+
+def case_linear(be, ar, M, K, N, act="gelu", seed=90):
+    """cfd_linear_fwd / cfd_linear_bwd."""
+    api, P = be.api, be.ptr
+    code = {"none": 0, "relu": 1, "tanh": 2, "gelu": 3, "swish": 4}[act]
+    rng = np.random.default_rng(seed)
+    dx = be.dev(rng.standard_normal((M, K)).astype(np.float32))
+    dw = be.dev((rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32))
+    db = be.dev(rng.standard_normal((N,)).astype(np.float32) * 0.3)
+    dgy = be.dev(rng.standard_normal((M, N)).astype(np.float32))
+    y, pre = ar.out((M, N)), ar.out((M, N))
+    wsf = ar.scratch(api.size("cfd_linear_fwd_workspace_bytes", M, K, N))
+    gx, gw, gb = ar.out((M, K)), ar.out((N, K)), ar.out((N,))
+    ws = ar.scratch(api.size("cfd_linear_bwd_workspace_bytes", M, K, N))
+    api.call("cfd_linear_fwd", P(dx), P(dw), P(db), P(y), P(pre), P(wsf), M, K, N, code, be.stream)
+    api.call("cfd_linear_bwd", P(dgy), P(dx), P(dw), P(y), P(pre), P(gx), P(gw), P(gb), P(ws), M, K, N, code, be.stream)
+    be.sync()
+    return {"y": be.host(y), "pre": be.host(pre), "gx": be.host(gx), "gw": be.host(gw), "gb": be.host(gb)}
+
+
+def case_deeponet_inner(be, ar, B, P_, Kq, HW, seed=91):
+    """cfd_deeponet_inner_fwd (residual at query indices) / cfd_deeponet_inner_bwd."""
+    api, P = be.api, be.ptr
+    rng = np.random.default_rng(seed)
+    dbr, dtr = be.dev(rng.standard_normal((B, P_)).astype(np.float32)), be.dev(rng.standard_normal((Kq, P_)).astype(np.float32))
+    dbi, du = be.dev(np.array([0.37], np.float32)), be.dev(rng.standard_normal((B, HW)).astype(np.float32))
+    dq, dg = be.dev(rng.integers(0, HW, size=Kq).astype(np.int32)), be.dev(rng.standard_normal((B, Kq)).astype(np.float32))
+    preds, gbr, gtr, gbi = ar.out((B, Kq)), ar.out((B, P_)), ar.out((Kq, P_)), ar.out((1,))
+    ws = ar.scratch(api.size("cfd_deeponet_inner_bwd_workspace_bytes", B, P_, Kq))
+    api.call("cfd_deeponet_inner_fwd", P(dbr), P(dtr), P(dbi), P(du), P(dq), P(preds), B, P_, Kq, HW, be.stream)
+    api.call("cfd_deeponet_inner_bwd", P(dg), P(dbr), P(dtr), P(gbr), P(gtr), P(gbi), P(ws), B, P_, Kq, be.stream)
+    be.sync()
+    return {"preds": be.host(preds), "gbranch": be.host(gbr), "gtrunk": be.host(gtr), "gbias": be.host(gbi)}
+
+
+# ---- which check runs each size function's entry point on a guarded scratch() of exactly that size --------------------
+# (tests/test_emul_hostile_memory.py fails if include/cfdbench_amd.h gains a size function this table does not name)
+WORKSPACE_COVERAGE = {
+    "cfd_spectral_wgrad_workspace_bytes": "check_mix_wgrad",
+    "cfd_spectral_conv2d_bwd_workspace_bytes": "check_spectral",
+    "cfd_chan_wgrad_workspace_bytes": "check_chanmix",
+    "cfd_fno_stem_bwd_workspace_bytes": "check_stem",
+    "cfd_fno_head_workspace_bytes": "check_head",
+    "cfd_loss_workspace_bytes": "check_loss_and_adam",
+    "cfd_label_energy_workspace_bytes": "check_head_train",
+    "cfd_gemm_workspace_bytes": "check_gemm",
+    "cfd_linear_fwd_workspace_bytes": "check_linear",
+    "cfd_linear_bwd_workspace_bytes": "check_linear",
+    "cfd_deeponet_inner_bwd_workspace_bytes": "check_deeponet_inner",
+    "cfd_ffn_stack_bwd_workspace_bytes": "check_ffn_stack",
+    "cfd_rowdot_bwd_workspace_bytes": "check_bcast_rowdot",
+    "cfd_conv2d_fwd_workspace_bytes": "check_conv2d",
+    "cfd_conv2d_bwd_workspace_bytes": "check_conv2d",
+    "cfd_conv2d_wfrag_bytes": "check_conv_prepared",
+    "cfd_batchnorm_workspace_bytes": "check_batchnorm",
+    "cfd_convt2_bwd_workspace_bytes": "check_convt",
+    "cfd_fno_workspace_bytes": "run_fno",
+    "cfd_fno_workspace_bytes_ex": "check_fno_bf16_storage",
+}

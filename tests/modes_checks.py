@@ -28,18 +28,18 @@ def run_fno(be, params, batch, L, C, H, W, p, m1, m2, which="nmse"):
     try:
         shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.zeros(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
+        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
         ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
-        ws = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
+        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        preds, sums, coef, scores = be.zeros((B, 2, H, W)), be.zeros((4,)), be.zeros((2,)), be.zeros((4,))
+        preds, sums, coef, scores = be.out((B, 2, H, W)), be.out((4,)), be.out((2,)), be.out((4,))
         sh, pr, gr = ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs)
         api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(ws), 1, be.stream)
         api.call("cfd_loss_coef", P(sums), P(coef), WHICH[which], 1.0, be.stream)
         api.call("cfd_fno_backward", plan, sh, pr, gr, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(ws), be.stream)
         api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
-        ws0 = be.bytes(api.size("cfd_fno_workspace_bytes", plan, sh, 0))
-        preds0 = be.zeros((B, 2, H, W))
+        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 0))
+        preds0 = be.out((B, 2, H, W))
         api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), None, P(preds0), None, P(ws0), 0, be.stream)
         be.sync()
         return {"preds": be.host(preds), "preds_infer": be.host(preds0), "scores": be.host(scores),
@@ -90,10 +90,11 @@ def check_train_step_deferred(be, B, C, L, H, W, m1, m2, p=5, which="mse", flags
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
         out = {}
         for fl in (0, flags):
-            flat, grad, m, v = be.dev(flat0), be.zeros((off,)), be.zeros((off,)), be.zeros((off,))
+            # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
+            flat, grad, m, v = be.dev(flat0), K.flat_grad_buffer(be, layout, off), be.zeros((off,)), be.zeros((off,))
             ps, gs = ctypes.byref(K._flat_struct(be, flat, layout, L)), ctypes.byref(K._flat_struct(be, grad, layout, L))
-            ws = be.bytes(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
-            preds, sums, coef = be.zeros((B, 2, H, W)), be.zeros((4,)), be.zeros((2,))
+            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
+            preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
             for step in range(1, steps + 1):
                 api.call("cfd_fno_forward_train_f", plan, sh, ps, gs, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(coef), P(ws),
                          WHICH[which], 1.0, 0, fl, be.stream)
@@ -107,7 +108,7 @@ def check_train_step_deferred(be, B, C, L, H, W, m1, m2, p=5, which="mse", flags
                     out[fl] = dict(g1=be.host(grad).copy(), sums1=be.host(sums).copy(), preds1=be.host(preds).copy())
             out[fl]["flat"] = be.host(flat).copy()
         a, b = out[0], out[flags]
-        res = {"bitwise": float(max(np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")))}
+        res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
         p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
         b64 = {k: v.astype(f64) for k, v in batch.items()}
         ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
@@ -131,11 +132,11 @@ def check_spectral_golden(be, g):
     plan = api.plan_create(H, W, m1, m2)
     try:
         dx, dgy, dw1, dw2 = be.dev(x), be.dev(gy), be.dev(w1), be.dev(w2)
-        xh, z = be.zeros((B, Cin, 2 * m1, m2), np.complex64), be.zeros((B, Cout, 2 * m1, m2), np.complex64)
-        y, gx = be.zeros((B, Cout, H, W)), be.zeros((B, Cin, H, W))
-        gw1, gw2 = be.zeros((Cin, Cout, m1, m2), np.complex64), be.zeros((Cin, Cout, m1, m2), np.complex64)
+        xh, z = be.out((B, Cin, 2 * m1, m2), np.complex64), be.out((B, Cout, 2 * m1, m2), np.complex64)
+        y, gx = be.out((B, Cout, H, W)), be.out((B, Cin, H, W))
+        gw1, gw2 = be.out((Cin, Cout, m1, m2), np.complex64), be.out((Cin, Cout, m1, m2), np.complex64)
         api.call("cfd_spectral_conv2d_fwd", plan, P(dx), P(dw1), P(dw2), P(y), P(xh), P(z), B, Cin, Cout, be.stream)
-        ws = be.bytes(api.size("cfd_spectral_conv2d_bwd_workspace_bytes", plan, B, Cin, Cout))
+        ws = be.scratch(api.size("cfd_spectral_conv2d_bwd_workspace_bytes", plan, B, Cin, Cout))
         api.call("cfd_spectral_conv2d_bwd", plan, P(dgy), P(xh), P(dw1), P(dw2), P(gx), P(gw1), P(gw2), P(ws), B, Cin, Cout, be.stream)
         be.sync()
         return {"y": nm(be.host(y), g["y"]), "gx": nm(be.host(gx), g["gx"]), "gw1": nm(be.host(gw1), g["gw1"]),
@@ -174,11 +175,11 @@ def check_refusals(be, C=8, B=1, H=64, W=64, m1=16, m2=16, L=1, p=5):
     try:
         shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.zeros(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
+        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
         ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        ws = be.bytes(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
-        preds, sums, coef = be.zeros((B, 2, H, W)), be.zeros((4,)), be.zeros((2,))
+        ws = be.scratch(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
+        preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
         sh, pr, gr = ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs)
         res["bf16_forward"] = _refused(be, "cfd_fno_forward_ex", plan, sh, pr, P(di), P(dc), P(dm), None, P(preds), None, P(ws), 0, 1,
                                        be.stream)

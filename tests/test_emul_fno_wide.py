@@ -12,6 +12,13 @@ def be():
     return NumpyBackend()
 
 
+@pytest.fixture(autouse=True)
+def _guard_bands_intact(be):
+    """Every buffer of tests/backends.py sits between guard bands: a write outside one fails the test that made it."""
+    yield
+    be.verify()
+
+
 def _assert_all(res, tol=K.TOL):
     bad = {k: v for k, v in res.items() if not (v < tol)}
     assert not bad, f"parity failures (tol {tol}): {bad}; all: {res}"

@@ -26,12 +26,12 @@ def check_chanmix_fwd(be, B, Ci, Co, HW, act, seed=2):
     g = rng.standard_normal((B, Co, HW)).astype(np.float32)
     f = O.gelu(x.astype(f64)) if act else x.astype(f64)
     res = {}
-    out = be.zeros((B, Co, HW))
+    out = be.out((B, Co, HW))
     dx, dw, db, dg = be.dev(x), be.dev(w), be.dev(b), be.dev(g)
     api.call("cfd_chanmix", P(dx), P(dw), P(db), P(out), B, Ci, Co, HW, int(act), 0, be.stream)
     be.sync()
     res["fwd"] = nm(be.host(out), np.einsum("oi,bip->bop", w.astype(f64), f) + b[None, :, None])
-    gin = be.zeros((B, Ci, HW))
+    gin = be.out((B, Ci, HW))
     api.call("cfd_chanmix", P(dg), P(dw), None, P(gin), B, Co, Ci, HW, 0, 1, be.stream)
     be.sync()
     res["bwd_in"] = nm(be.host(gin), np.einsum("oi,bop->bip", w.astype(f64), g.astype(f64)))
@@ -51,11 +51,11 @@ def check_stem_fwd(be, B, H, W, P_, C, border, seed=3):
         res = {}
         di, dm, dc = (be.dev(batch[k]) for k in ("inputs", "mask", "case_params"))
         dw, db = be.dev(w), be.dev(b)
-        out = be.zeros((B, C, H, W))
+        out = be.out((B, C, H, W))
         api.call("cfd_fno_stem_fwd", plan, P(di), P(dm), P(dc), P(dw), P(db), P(out), B, 2, P_, C, be.stream)
         be.sync()
         res["fwd"] = nm(be.host(out), O.conv1x1(feats, w.astype(f64), b.astype(f64)))
-        out2 = be.zeros((B, C, H, W))
+        out2 = be.out((B, C, H, W))
         api.call("cfd_fno_stem_fwd", plan, P(di), None, P(dc), P(dw), P(db), P(out2), B, 2, P_, C, be.stream)
         be.sync()
         feats1 = O.assemble_features(batch["inputs"].astype(f64), batch["case_params"].astype(f64),
@@ -85,8 +85,8 @@ def check_head_fwd(be, B, C, HW, act, Co=2, border=True, seed=4):
     d = preds - Lb * M
     ref_sums = np.array([(d * d).sum(), np.abs(d).sum(), ((Lb * M) ** 2).sum(), B * Co * HW])
     dv = {k: be.dev(v) for k, v in dict(a=a, mask=mask, label=label, w1=w1, b1=b1, w2=w2, b2=b2).items()}
-    ws = be.bytes(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW))
-    out, sums = be.zeros((B, Co, HW)), be.zeros((4,))
+    ws = be.scratch(api.size("cfd_fno_head_workspace_bytes", B, C, Hd, Co, HW))
+    out, sums = be.out((B, Co, HW)), be.out((4,))
     api.call("cfd_fno_head_fwd", P(dv["a"]), P(dv["mask"]), P(dv["label"]), P(dv["w1"]), P(dv["b1"]), P(dv["w2"]), P(dv["b2"]),
              P(out), P(sums), P(ws), B, C, Hd, Co, HW, int(act), be.stream)
     be.sync()
@@ -95,7 +95,7 @@ def check_head_fwd(be, B, C, HW, act, Co=2, border=True, seed=4):
     for k in range(3):
         res[f"sum{k}"] = nm(hs[k:k + 1], ref_sums[k:k + 1])
     res["count"] = abs(hs[3] - ref_sums[3])
-    out2 = be.zeros((B, Co, HW))
+    out2 = be.out((B, Co, HW))
     api.call("cfd_fno_head_fwd", P(dv["a"]), None, None, P(dv["w1"]), P(dv["b1"]), P(dv["w2"]), P(dv["b2"]), P(out2), None, None,
              B, C, Hd, Co, HW, int(act), be.stream)
     be.sync()
@@ -116,14 +116,14 @@ def run_fno_forward(be, params, batch, L, C, H, W, p, act_dtype=0):
         ps = K.make_param_struct(be, pd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
         out = {}
-        ws = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-        preds, sums = be.zeros((B, 2, H, W)), be.zeros((4,))
+        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
+        preds, sums = be.out((B, 2, H, W)), be.out((4,))
         api.call("cfd_fno_forward_ex", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds), P(sums),
                  P(ws), 1, act_dtype, be.stream)
         be.sync()
         out["preds"], out["sums"] = be.host(preds), be.host(sums)
-        ws0 = be.bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
-        preds0 = be.zeros((B, 2, H, W))
+        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
+        preds0 = be.out((B, 2, H, W))
         api.call("cfd_fno_forward_ex", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), None, P(preds0), None,
                  P(ws0), 0, act_dtype, be.stream)
         be.sync()
@@ -165,11 +165,11 @@ def check_wide_refusals(be, C=64, B=1, H=64, W=64, L=1, p=5):
     try:
         shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.zeros(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
+        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
         ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        ws = be.bytes(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
-        preds, sums, coef = be.zeros((B, 2, H, W)), be.zeros((4,)), be.zeros((2,))
+        ws = be.scratch(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
+        preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
         sh, pr, gr = ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs)
         return {
             "bf16_forward": refused(be, "cfd_fno_forward_ex", plan, sh, pr, P(di), P(dc), P(dm), None, P(preds), None, P(ws), 0, 1,
