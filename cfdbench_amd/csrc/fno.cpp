@@ -76,6 +76,9 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     CFD_REQUIRE(s->hidden >= 1 && s->hidden <= CFD_WIDE_MAX, CFD_ERR_UNSUPPORTED, "%s: hidden=%d (max %d)", fn, s->hidden, CFD_WIDE_MAX);
     CFD_REQUIRE(s->hidden <= 32 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: hidden=%d: bf16 activation storage needs hidden <= 32", fn,
                 s->hidden);
+    CFD_REQUIRE(s->out_chan >= 1 && s->out_chan <= 8, CFD_ERR_UNSUPPORTED, "%s: out_chan=%d (max 8) unsupported", fn, s->out_chan);
+    CFD_REQUIRE(s->out_chan <= 2 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: out_chan=%d: bf16 activation storage needs out_chan <= 2", fn,
+                s->out_chan);
     CFD_REQUIRE(!p->many || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED,
                 "%s: modes (%d,%d): bf16 activation storage needs modes1 <= 15 and modes2 <= 16", fn, p->m1, p->m2);
     return CFD_OK;
@@ -89,9 +92,9 @@ Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, ch
                   const void* mask) {
     const int B = s->B, C = s->hidden, NL = s->num_layers;
     Deferred d{};
-    // the wide route (hidden > 32) and the many-modes route have none of the fused kernels that carry a deferred job: every flag is
-    // ignored there
-    if (C > 32 || p->many) return d;
+    // the wide route (hidden > 32), the many-modes route and the head's channel route (out_chan > 2) have none of the fused kernels
+    // that carry a deferred job: every flag is ignored there
+    if (C > 32 || p->many || s->out_chan > 2) return d;
     d.scale = (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     const float* gA = (const float*)(base + L.off_gA);
     const float* gB = (const float*)(base + L.off_gB);

@@ -338,15 +338,24 @@ extern "C" size_t cfd_fno_head_workspace_bytes(int B, int C, int Hd, int Co, int
     return r > wide ? r : wide;
 }
 
+#define HEAD_CO_MAX 8  // out_chan: 1 .. 2 on the pair kernels, 3 .. 8 on the channel route (k_head_fwd_co / k_head_bwd_co)
 static int head_check(const char* fn, int B, int C, int Hd, int Co, int HW) {
     CFD_REQUIRE(B >= 0 && C >= 1 && HW >= 1, CFD_ERR_INVALID_ARG, "%s: bad sizes", fn);
     CFD_REQUIRE(Hd == HEAD_HD, CFD_ERR_UNSUPPORTED, "%s: head width %d unsupported (the reference hard-codes 128, fno2d.py:175)", fn, Hd);
     CFD_REQUIRE(C <= 32, CFD_ERR_UNSUPPORTED, "%s: hidden=%d (max 32) unsupported", fn, C);
     CFD_REQUIRE((long)B * ((HW + 63) / 64) < (1L << 30), CFD_ERR_UNSUPPORTED, "%s: B * ceil(HW / 64) = %ld tiles (max 2^30)", fn,
                 (long)B * ((HW + 63) / 64));
-    CFD_REQUIRE(Co >= 1 && Co <= 2, CFD_ERR_UNSUPPORTED, "%s: out_chan=%d (max 2) unsupported", fn, Co);
+    CFD_REQUIRE(Co >= 1 && Co <= HEAD_CO_MAX, CFD_ERR_UNSUPPORTED, "%s: out_chan=%d (max %d) unsupported", fn, Co, HEAD_CO_MAX);
     return CFD_OK;
 }
+
+// launchers of the channel route (out_chan 3 .. 8; defined behind its kernels at the end of this file)
+static int head_fwd_co(const float* a, const float* mask, const float* label, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* preds, float* sums, void* ws, int B, int C, int Co, int HW, int act_in, hipStream_t st,
+                       bool all_sums);
+static int head_bwd_co(const float* a, const float* mask, const float* label, const float* preds, const float* gext, const float* coef,
+                       const float* w1, const float* b1, const float* w2, float* ga, float* gw1, float* gb1, float* gw2, float* gb2,
+                       void* ws, int B, int C, int Co, int HW, int act_in, hipStream_t st);
 
 extern "C" int cfd_fno_head_fwd(const float* a, const float* mask, const float* label, const float* w1, const float* b1,
                                 const float* w2, const float* b2, float* preds, float* sums, void* ws, int B, int C,
@@ -367,8 +376,10 @@ int cfd_int_fno_head_fwd(const void* a_, const float* mask, const float* label, 
         return cfd_int_wide_head_fwd(a, mask, label, w1, b1, w2, b2, preds, sums, ws, B, C, Co, HW, act_in, stream);
     }
     CFD_TRY(head_check("cfd_fno_head_fwd", B, C, Hd, Co, HW));
+    CFD_REQUIRE(Co <= 2 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_head_fwd: bf16 activation storage needs out_chan <= 2 (out_chan=%d)", Co);
     if (B == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (Co > 2) return head_fwd_co(a, mask, label, w1, b1, w2, b2, preds, sums, ws, B, C, Co, HW, act_in, st, true);  // channel route
     const int blocks = head_blocks(B, HW, true, C);
     float* part = label ? (float*)ws : nullptr;
     const bool v4 = dt == CFD_DT_F32 && HW % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)preds % 16) == 0;
@@ -999,6 +1010,582 @@ CFD_UNROLL(CFD_HB_UNROLL)
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// out_chan 3 .. 8: the channel route (chosen by the launchers; out_chan <= 2 keeps the kernels above)
+// ------------------------------------------------------------------------------------------------------
+// The same tiling as k_head_fwd / k_head_bwd (fp32 activations, fc1 always on the three-piece split: six MFMAs per product), with fc2 and
+// everything behind it written over NCO = 4 or 8 channel slots (slots >= Co carry zero weights and zero gradients):
+//   forward   s_w2[pair of hidden units][slot] holds (w2[c][2p], w2[c][2p+1]); a lane folds the GELU pair into NCO packed accumulators
+//             (one ds_read_b128 per two slots), the four lane groups are summed per slot in slot order, and lane group q keeps slots q
+//             and q + 4 of its four pixels -- the stores, labels and loss terms of a lane stay at NCO / 4 channels.
+//   backward  wave w fetches and forms the upstream gradient of slots w and w + 4 (lane = pixel) and owns their gb2 sums; the tile's
+//             gradients go through s_gr[column][slot], fc2's weights stay in LDS (s_w2[slot][hidden], read per phase: eight slots of
+//             a lane's eight hidden units would be 64 loop-invariant registers), gw2 has NCO x 8 per-lane accumulators, and
+//             d/dg = sum_c w2[c][j] dout[c] is an FMA chain in slot order.
+// The partial-sum record keeps the layout of head_part_floats(C, Co).  Planes are loaded with the unaligned 16-byte form on every grid.
+
+template <int CQ, bool ACT, int NCO>
+__global__ __launch_bounds__(256, 2) void k_head_fwd_co(const float* __restrict__ a, const float* __restrict__ mask,
+                                                  const float* __restrict__ label, const float* __restrict__ w1,
+                                                  const float* __restrict__ b1, const float* __restrict__ w2,
+                                                  const float* __restrict__ b2, float* __restrict__ preds,
+                                                  float* __restrict__ part, int B, int C, int Co, int HW) {
+    constexpr int AP = 3, NK = NCO / 4;
+    static_assert(NCO == 4 || NCO == 8, "channel slots: one or two per lane group");
+    __shared__ bf16x8 s_w1[AP * HEAD_MT * 64];  // [piece][M tile][lane]
+    __shared__ __attribute__((aligned(16))) float s_b1[HEAD_HD];
+    __shared__ __attribute__((aligned(16))) cfd_f2 s_w2[(HEAD_HD / 2) * NCO];  // [pair of hidden units][slot]
+    __shared__ float s_red[12];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = lane >> 4, n = lane & 15;
+    float lsq = 0.f, labs = 0.f, ll2 = 0.f;
+    const int tpb = (HW + 63) / 64;
+    const int total = B * tpb;  // < 2^30 (checked by the launcher)
+    const int stride = (int)gridDim.x * 4;
+    int tile = (int)blockIdx.x * 4 + wave;
+    int b = -1, px = 0;
+    auto locate = [&](int t, int& bb, int& pp) {
+        bb = -1;
+        pp = 0;
+        if (t < total) {
+            const unsigned ub = (unsigned)t / (unsigned)tpb;
+            bb = (int)ub;
+            pp = (int)((unsigned)t - ub * (unsigned)tpb) * 64 + 4 * n;
+        }
+    };
+    float hn[CQ][4];           // raw activations of the next tile
+    float mkn[4], lbn[NK][4];  // mask / label (channels q, q + 4) of the next tile's four pixels
+    auto fetch_io = [&](int bb, int pp) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool ok = bb >= 0 && pp + j < HW;
+            mkn[j] = (ok && mask) ? mask[(size_t)bb * HW + pp + j] : 1.f;
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                lbn[k][j] = (ok && label && q + 4 * k < Co) ? label[((size_t)bb * Co + q + 4 * k) * HW + pp + j] : 0.f;
+        }
+    };
+    locate(tile, b, px);
+    head_load_raw<CQ, false, float>(a, b, C, HW, px, q, hn);
+    fetch_io(b, px);
+    head_build_w1f<AP>(s_w1, w1, C, CQ);
+#pragma unroll
+    for (int i0 = 0; i0 < HEAD_HD; i0 += 256) {
+        const int i = i0 + (int)threadIdx.x;
+        if (i < HEAD_HD) s_b1[i] = b1[i];
+    }
+#pragma unroll
+    for (int i0 = 0; i0 < (HEAD_HD / 2) * NCO; i0 += 256) {
+        const int i = i0 + (int)threadIdx.x;
+        if (i < (HEAD_HD / 2) * NCO) {
+            const int p = i / NCO, c = i % NCO;
+            s_w2[i] = c < Co ? cfd_f2{w2[c * HEAD_HD + 2 * p], w2[c * HEAD_HD + 2 * p + 1]} : cfd_f2{0.f, 0.f};
+        }
+    }
+    float b2v[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) b2v[k] = q + 4 * k < Co ? b2[q + 4 * k] : 0.f;
+    // this lane's group as four all-ones / zero masks: written as a select chain over q, `tot[q]` below becomes an indexed load from a
+    // four-float array in scratch memory (four stores and a load in every pixel phase)
+    unsigned gsel[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) gsel[g] = (unsigned)cfd_opaque(q == g ? -1 : 0);
+    __syncthreads();
+    for (; tile < total; tile += stride) {
+        float h[CQ][4], mk[4], lb[NK][4];
+#pragma unroll
+        for (int c = 0; c < CQ; ++c)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) h[c][j] = hn[c][j];
+        head_mask_raw<CQ, false, float>(h, b, C, HW, px, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            mk[j] = mkn[j];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) lb[k][j] = lbn[k][j];
+        }
+        const int bc = b, pxc = px;
+        locate(tile + stride, b, px);
+        head_load_raw<CQ, false, float>(a, b, C, HW, px, q, hn);
+        fetch_io(b, px);
+        cfd_sched_fence();  // the prefetch stays here, ahead of this tile's arithmetic
+        if constexpr (ACT) head_act<CQ>(h);
+        float out[NK][4];  // the phase being processed lands in out[k][3]; registers rotate each trip
+#pragma unroll
+        for (int k = 0; k < NK; ++k) out[k][0] = out[k][1] = out[k][2] = out[k][3] = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            const int lo = cfd_opaque(lane), q4 = 4 * cfd_opaque(q);  // keep the LDS table reads inside the loop
+            float xk[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) xk[c] = c < CQ ? h[c < CQ ? c : 0][0] : 0.f;
+            const CfdAct8<AP> bs = cfd_act_split8<AP>(xk);
+            f32x4 z[HEAD_MT];
+#pragma unroll
+            for (int mt = 0; mt < HEAD_MT; ++mt) {
+                const float4 bq = *reinterpret_cast<const float4*>(s_b1 + 16 * mt + q4);
+                z[mt] = f32x4{bq.x, bq.y, bq.z, bq.w};
+            }
+#pragma unroll
+            for (int k = 0; k < cfd_nterm_aa(AP); ++k)
+#pragma unroll
+                for (int mt = 0; mt < HEAD_MT; ++mt)
+                    z[mt] = cfd_mfma16x16x32_bf16(s_w1[(cfd_term_aa_a(AP, k) * HEAD_MT + mt) * 64 + lo], bs.p[cfd_term_aa_b(AP, k)], z[mt]);
+            cfd_f2 o[NCO];  // per slot: partial sums over the even / odd hidden units of this lane
+#pragma unroll
+            for (int c = 0; c < NCO; ++c) o[c] = cfd_f2{0.f, 0.f};
+#pragma unroll
+            for (int mt = 0; mt < HEAD_MT; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; r += 2) {
+                    const int jh = 16 * mt + q4 + r;
+                    const cfd_f2 gl = cfd_gelu2(cfd_f2{z[mt][r], z[mt][r + 1]});
+                    const cfd_f2* wp = s_w2 + (jh >> 1) * NCO;
+#pragma unroll
+                    for (int c = 0; c < NCO; c += 2) {
+                        const float4 wq = *reinterpret_cast<const float4*>(wp + c);  // slots c, c + 1
+                        o[c] = cfd_fma2(cfd_f2{wq.x, wq.y}, gl, o[c]);
+                        o[c + 1] = cfd_fma2(cfd_f2{wq.z, wq.w}, gl, o[c + 1]);
+                    }
+                }
+            float tot[NCO];  // sums over the four lane groups, slot by slot
+#pragma unroll
+            for (int c = 0; c < NCO; ++c) tot[c] = cfd_row_sum4(cfd_hsum2(o[c]));
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                unsigned ob = 0u;  // slot q + 4k, picked with this lane's bit masks
+#pragma unroll
+                for (int g = 0; g < 4; ++g) ob |= __builtin_bit_cast(unsigned, tot[4 * k + g]) & gsel[g];
+                const float ov = __builtin_bit_cast(float, ob);
+                out[k][0] = out[k][1]; out[k][1] = out[k][2]; out[k][2] = out[k][3]; out[k][3] = ov;
+            }
+#pragma unroll
+            for (int c = 0; c < CQ; ++c) { h[c][0] = h[c][1]; h[c][1] = h[c][2]; h[c][2] = h[c][3]; }
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int c = q + 4 * k;  // lane group q stores channels q and q + 4
+            if (c < Co) {
+                float pv[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool ok = pxc + j < HW;
+                    pv[j] = (out[k][j] + b2v[k]) * mk[j];  // fno2d.py:233
+                    if (label && ok) {
+                        const float lab = lb[k][j] * mk[j];  // fno2d.py:236
+                        const float d = pv[j] - lab;
+                        lsq = fmaf(d, d, lsq);
+                        labs += fabsf(d);
+                        ll2 = fmaf(lab, lab, ll2);
+                    }
+                }
+                float* dst = preds + ((size_t)bc * Co + c) * HW + pxc;
+                if (pxc + 3 < HW) {
+                    cfd_st4u(dst, make_float4(pv[0], pv[1], pv[2], pv[3]));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (pxc + j < HW) dst[j] = pv[j];
+                }
+            }
+        }
+    }
+    if (part) {
+        lsq = cfd_wave_sum(lsq); labs = cfd_wave_sum(labs); ll2 = cfd_wave_sum(ll2);
+        if (lane == 0) { s_red[wave] = lsq; s_red[4 + wave] = labs; s_red[8 + wave] = ll2; }
+        __syncthreads();
+        if (threadIdx.x < 3) {
+            const float* s = s_red + 4 * threadIdx.x;
+            part[blockIdx.x * 3 + threadIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+        }
+    }
+}
+
+// sums[0..1] only: the training head's forward half (sums[2..3] and the coefficients came from cfd_label_energy_coef)
+__global__ __launch_bounds__(64) void k_head_loss_final01(const float* __restrict__ part, int nblk, float* __restrict__ sums) {
+    const int lane = threadIdx.x;
+    float a = 0.f, b = 0.f;
+    for (int k = lane; k < nblk; k += 64) { a += part[k * 3]; b += part[k * 3 + 1]; }
+    a = cfd_wave_sum(a); b = cfd_wave_sum(b);
+    if (lane == 0) { sums[0] = a; sums[1] = b; }
+}
+
+// k_head_bwd's stand-alone form (no FUSE, four waves, single-buffered input planes) over NCO channel slots.
+template <int KS, bool ACT, int NCO>
+__global__ __launch_bounds__(256, NCO == 8 ? 1 : 2) void k_head_bwd_co(
+    const float* __restrict__ a, const float* __restrict__ mask, const float* __restrict__ label,
+    const float* __restrict__ preds, const float* __restrict__ gext, const float* __restrict__ coef,
+    const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2, float* __restrict__ ga,
+    float* __restrict__ part, int B, int C, int Co, int HW) {
+    constexpr int AP = 3, NWV = 4, NK = NCO / 4;
+    static_assert(NCO == 4 || NCO == 8, "channel slots: one or two per wave");
+    constexpr int CP = 4 * KS;
+    constexpr int MU = (CP + 15) / 16;
+    constexpr int LDK = 40, LDT = 72, LDX = 40;
+    constexpr int HT = 2, HPW = 32, NTH = 256;
+    constexpr int NST = (CP * 16 + NTH - 1) / NTH;
+    constexpr int HTR = CP + 1;
+    __shared__ __attribute__((aligned(16))) __bf16 s_hk[AP][64 * LDK];         // [piece][column][channel]
+    __shared__ __attribute__((aligned(16))) __bf16 s_ht[AP][HTR * LDT];        // [piece][channel][column]
+    __shared__ __attribute__((aligned(16))) __bf16 s_x[NWV][AP][HPW * LDX];    // [wave][piece][hidden][32 columns]
+    __shared__ float4 s_red[NWV * CP * 16];                                    // [wave][channel][16 x float4 = 64 pixels] partial d/dh
+    __shared__ __attribute__((aligned(16))) float s_gr[64 * NCO];              // [column][slot] upstream gradient on the raw head output
+    __shared__ __attribute__((aligned(16))) float s_w2[NCO * HEAD_HD];         // [slot][hidden]
+    const int lane = threadIdx.x & 63, wave = cfd_uniform(threadIdx.x >> 6);
+    const int q = lane >> 4, n = lane & 15;
+    __bf16* s_xw = s_x[wave][0];
+    CfdAct8<AP> w1f[HT];
+    CfdAct8<AP> w1t[MU];
+    float bz[HT][4];
+    const float c0 = label ? coef[0] : 0.f, c1 = label ? coef[1] : 0.f;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 aw1[HT][MU];
+    cfd_f2 acc2[NCO][HT][2], accb1[HT][2];
+#pragma unroll
+    for (int t = 0; t < HT; ++t) {
+#pragma unroll
+        for (int v = 0; v < MU; ++v) aw1[t][v] = zero;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            accb1[t][v] = cfd_f2{0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < NCO; ++c) acc2[c][t][v] = cfd_f2{0.f, 0.f};
+        }
+    }
+    float gb2a[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) gb2a[k] = 0.f;
+    const int tpb = (HW + 63) / 64;
+    const int total = B * tpb;  // < 2^30 (checked by the launcher)
+    struct TileAt { int b, px0; };
+    auto locate = [&](int tile) -> TileAt {
+        if (tile >= total) return TileAt{-1, 0};
+        const unsigned ub = (unsigned)tile / (unsigned)tpb;
+        return TileAt{(int)ub, (int)((unsigned)tile - ub * (unsigned)tpb) * 64};
+    };
+    float4 raw[NST];
+    float4 gp_cur[NST], gp_next[NST];
+    // upstream gradient of the tile's 64 pixels: wave w owns slots w and w + 4 (lane = pixel), fetched / staged with the activations
+    float rmk = 0.f, rpr[NK], rlb[NK], rge[NK];
+    bool rok = false;
+    auto fetch_gr = [&](const TileAt t) {
+        const int pix = t.px0 + lane;
+        rok = t.b >= 0 && pix < HW;
+        rmk = 1.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) rpr[k] = rlb[k] = rge[k] = 0.f;
+        if (rok) {
+            if (mask) rmk = mask[(size_t)t.b * HW + pix];
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                if (wave + 4 * k < Co) {
+                    const size_t off = ((size_t)t.b * Co + wave + 4 * k) * HW + pix;
+                    if (gext) rge[k] = gext[off];
+                    if (label) { rpr[k] = preds[off]; rlb[k] = label[off]; }
+                }
+        }
+    };
+    auto stage_gr = [&]() {
+        const int col = 16 * (lane & 3) + (lane >> 2);  // pixel 4n + j -> column 16j + n
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            float g = 0.f;
+            if (rok && wave + 4 * k < Co) {
+                float gp = rge[k];
+                if (label) {
+                    const float d = rpr[k] - rlb[k] * rmk;
+                    const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                    gp += c0 * 2.f * d + c1 * sg;
+                }
+                g = gp * rmk;
+            }
+            gb2a[k] += g;
+            s_gr[col * NCO + wave + 4 * k] = g;
+        }
+    };
+    auto fetch = [&](const TileAt t) {  // raw activations of the tile -> registers (zeros past the end of the work / image)
+#pragma unroll
+        for (int k = 0; k < NST; ++k) {
+            const int e = threadIdx.x + NTH * k;
+            const int i = e >> 4, n4 = e & 15;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t.b >= 0 && i < C) {
+                const int p4 = t.px0 + 4 * n4;
+                const float* src = a + ((size_t)t.b * C + i) * HW + p4;
+                if (p4 + 3 < HW) {
+                    v = cfd_ld4u(src);
+                } else {
+                    if (p4 < HW) v.x = src[0];
+                    if (p4 + 1 < HW) v.y = src[1];
+                    if (p4 + 2 < HW) v.z = src[2];
+                    if (p4 + 3 < HW) v.w = src[3];
+                }
+            }
+            raw[k] = v;
+        }
+    };
+    auto stage = [&]() {  // registers -> f(a) -> three bf16 pieces -> both operand layouts
+#pragma unroll
+        for (int k = 0; k < NST; ++k) {
+            const int e = threadIdx.x + NTH * k;
+            const int i = e >> 4, n4 = e & 15;
+            if (i < C) {
+                float4 v = raw[k];
+                if constexpr (ACT) {
+                    cfd_f2 P0, e0, P1, e1;
+                    const cfd_f2 x0 = {v.x, v.y}, x1 = {v.z, v.w};
+                    cfd_gelu_terms2(x0, P0, e0);
+                    cfd_gelu_terms2(x1, P1, e1);
+                    const cfd_f2 g0 = cfd_fma2(x0 * (cfd_f2)(CFD_INV_SQRT_2PI), e0, P0), g1 = cfd_fma2(x1 * (cfd_f2)(CFD_INV_SQRT_2PI), e1, P1);
+                    gp_next[k] = make_float4(g0.x, g0.y, g1.x, g1.y);
+                    const cfd_f2 f0 = x0 * P0, f1 = x1 * P1;
+                    v = make_float4(f0.x, f0.y, f1.x, f1.y);
+                }
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int col = 16 * j + n4;
+                    float r = vv[j];  // truncating pieces: pc0 + pc1 + pc2 == the value exactly
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        const unsigned hb = __builtin_bit_cast(unsigned, r) & 0xffff0000u;
+                        const __bf16 pv = __builtin_bit_cast(__bf16, (unsigned short)(hb >> 16));
+                        s_hk[pc][col * LDK + i] = pv;
+                        s_ht[pc][i * LDT + col] = pv;
+                        r -= __builtin_bit_cast(float, hb);
+                    }
+                }
+            }
+        }
+    };
+    TileAt t0 = locate((int)blockIdx.x), t1 = locate((int)blockIdx.x + (int)gridDim.x);
+    fetch(t0);
+    fetch_gr(t0);
+    for (int i = threadIdx.x; i < AP * 64 * LDK; i += NTH) (&s_hk[0][0])[i] = (__bf16)0.f;
+    for (int i = threadIdx.x; i < AP * HTR * LDT; i += NTH) (&s_ht[0][0])[i] = (__bf16)0.f;
+    for (int i = threadIdx.x; i < NCO * HEAD_HD; i += NTH) s_w2[i] = i < Co * HEAD_HD ? w2[i] : 0.f;
+    {
+        float x[8];
+#pragma unroll
+        for (int t = 0; t < HT; ++t) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) x[v] = (8 * q + v < C) ? w1[(HPW * wave + 16 * t + n) * C + 8 * q + v] : 0.f;
+            w1f[t] = cfd_act_split8<AP>(x);
+        }
+#pragma unroll
+        for (int mu = 0; mu < MU; ++mu) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                const int jh = HPW * wave + 16 * (v >> 2) + 4 * q + (v & 3);
+                x[v] = (16 * mu + n < C) ? w1[jh * C + 16 * mu + n] : 0.f;
+            }
+            w1t[mu] = cfd_act_split8<AP>(x);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < HT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bz[t][r] = b1[HPW * wave + 16 * t + 4 * q + r];
+    __syncthreads();  // planes zeroed
+    stage();
+    stage_gr();
+#pragma unroll
+    for (int k = 0; k < NST; ++k) gp_cur[k] = gp_next[k];
+    fetch(t1);
+    fetch_gr(t1);
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {  // all four waves walk the same tiles
+        const int b = t0.b;
+        const int px0 = t0.px0;
+        float* s_redf = reinterpret_cast<float*>(s_red);
+        const __bf16* hk = s_hk[0];  // piece pc at + pc * 64 * LDK
+        const __bf16* ht = s_ht[0];  // piece pc at + pc * HTR * LDT
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            // 1. recompute this wave's slice of the hidden pre-activation z[hidden][pixel n]
+            const int col = 16 * j + n;
+            f32x4 z[HT];
+            {
+                bf16x8 hp[AP];
+#pragma unroll
+                for (int pc = 0; pc < AP; ++pc) hp[pc] = *reinterpret_cast<const bf16x8*>(hk + pc * 64 * LDK + col * LDK + 8 * q);
+#pragma unroll
+                for (int t = 0; t < HT; ++t) z[t] = f32x4{bz[t][0], bz[t][1], bz[t][2], bz[t][3]};
+#pragma unroll
+                for (int k = 0; k < cfd_nterm_aa(AP); ++k)
+#pragma unroll
+                    for (int t = 0; t < HT; ++t) z[t] = cfd_mfma16x16x32_bf16(w1f[t].p[cfd_term_aa_a(AP, k)], hp[cfd_term_aa_b(AP, k)], z[t]);
+            }
+            // 2. a1 = gelu(z) feeds the fc2 weight gradient; gz = (W2^T graw) * gelu'(z), k-slot 4t + r
+            float gv[NCO];
+            {
+                const float* gp = s_gr + cfd_opaque(col * NCO);
+#pragma unroll
+                for (int c = 0; c < NCO; c += 4) {
+                    const float4 g4 = *reinterpret_cast<const float4*>(gp + c);
+                    // each value in a register of its own: broadcast into a packed operand from the HIGH half of a register pair, the
+                    // multiply would take the operand-select form that build.py's lint refuses
+                    gv[c] = cfd_opaque_f(g4.x); gv[c + 1] = cfd_opaque_f(g4.y); gv[c + 2] = cfd_opaque_f(g4.z); gv[c + 3] = cfd_opaque_f(g4.w);
+                }
+            }
+            const float* wq = s_w2 + cfd_opaque(HPW * wave + 4 * q);  // opaque: the weight reads stay inside the phase loop
+            float gzv[8];
+#pragma unroll
+            for (int t = 0; t < HT; ++t) {
+                cfd_f2 a1[2], ga1[2];
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const cfd_f2 zz = {z[t][2 * v], z[t][2 * v + 1]};
+                    cfd_f2 Phi, e;
+                    cfd_gelu_terms2(zz, Phi, e);
+                    a1[v] = zz * Phi;
+                    ga1[v] = cfd_fma2(zz * (cfd_f2)(CFD_INV_SQRT_2PI), e, Phi);  // gelu'(z) for now
+                }
+                cfd_f2 gs[2] = {cfd_f2{0.f, 0.f}, cfd_f2{0.f, 0.f}};
+#pragma unroll
+                for (int c = 0; c < NCO; ++c) {  // slot order: fixed summation order
+                    const float4 w4 = *reinterpret_cast<const float4*>(wq + c * HEAD_HD + 16 * t);
+                    const cfd_f2 g = (cfd_f2)(gv[c]);
+                    acc2[c][t][0] = cfd_fma2(g, a1[0], acc2[c][t][0]);
+                    acc2[c][t][1] = cfd_fma2(g, a1[1], acc2[c][t][1]);
+                    gs[0] = cfd_fma2(cfd_f2{w4.x, w4.y}, g, gs[0]);
+                    gs[1] = cfd_fma2(cfd_f2{w4.z, w4.w}, g, gs[1]);
+                }
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const cfd_f2 gz = gs[v] * ga1[v];
+                    accb1[t][v] = accb1[t][v] + gz;
+                    gzv[4 * t + 2 * v] = gz.x;
+                    gzv[4 * t + 2 * v + 1] = gz.y;
+                }
+            }
+            const CfdAct8<AP> gsp = cfd_act_split8<AP>(gzv);
+            // 3. transposed gz planes of this wave: row = local hidden unit 16t + 4q + r, column 16(j&1) + n
+            const int xcol = 16 * (j & 1) + n;
+#pragma unroll
+            for (int v = 0; v < 4 * HT; ++v) {
+                const int row = 16 * (v >> 2) + 4 * q + (v & 3);
+#pragma unroll
+                for (int pc = 0; pc < AP; ++pc) s_xw[pc * HPW * LDX + row * LDX + xcol] = gsp.p[pc][v];
+            }
+            // 4. partial d/dh[channel][pixel] = sum over this wave's hidden units w1[jh][channel] gz[jh][pixel]
+            f32x4 ghc[MU];
+#pragma unroll
+            for (int mu = 0; mu < MU; ++mu) ghc[mu] = zero;
+#pragma unroll
+            for (int k = 0; k < cfd_nterm_aa(AP); ++k)
+#pragma unroll
+                for (int mu = 0; mu < MU; ++mu) ghc[mu] = cfd_mfma16x16x32_bf16(w1t[mu].p[cfd_term_aa_a(AP, k)], gsp.p[cfd_term_aa_b(AP, k)], ghc[mu]);
+#pragma unroll
+            for (int mu = 0; mu < MU; ++mu)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * mu + 4 * q + r;
+                    if (i < CP) s_redf[((wave * CP + i) * 16 + n) * 4 + j] = ghc[mu][r];
+                }
+            // 5. after each pair of phases: gw1[hidden][channel] += sum over 32 pixels gz[hidden][px] h[channel][px]
+            if (j & 1) {
+                cfd_wave_lds_sync();
+                bf16x8 ap[HT][AP], bp[MU][AP];
+#pragma unroll
+                for (int t = 0; t < HT; ++t) {
+                    const int o = (16 * t + n) * LDX + 8 * q;
+#pragma unroll
+                    for (int pc = 0; pc < AP; ++pc) ap[t][pc] = *reinterpret_cast<const bf16x8*>(s_xw + pc * HPW * LDX + o);
+                }
+#pragma unroll
+                for (int mu = 0; mu < MU; ++mu) {
+                    const int o = (16 * mu + n < CP ? 16 * mu + n : CP) * LDT + 16 * (j - 1) + 8 * q;
+#pragma unroll
+                    for (int pc = 0; pc < AP; ++pc) bp[mu][pc] = *reinterpret_cast<const bf16x8*>(ht + pc * HTR * LDT + o);
+                }
+#pragma unroll
+                for (int k = 0; k < cfd_nterm_aa(AP); ++k)
+#pragma unroll
+                    for (int t = 0; t < HT; ++t)
+#pragma unroll
+                        for (int mu = 0; mu < MU; ++mu)
+                            aw1[t][mu] = cfd_mfma16x16x32_bf16(ap[t][cfd_term_aa_a(AP, k)], bp[mu][cfd_term_aa_b(AP, k)], aw1[t][mu]);
+                cfd_wave_lds_sync();
+            }
+        }
+        __syncthreads();
+        // next tile's input planes (every wave has finished reading this tile's), then the loads two tiles ahead
+        stage();
+        stage_gr();
+        const TileAt t2 = locate(tile + 2 * (int)gridDim.x);
+        fetch(t2);
+        fetch_gr(t2);
+        // ga[b][i][px0 .. px0+63] = (sum over the four hidden slices) * f'(a)
+#pragma unroll
+        for (int k = 0; k < NST; ++k) {
+            const int e = threadIdx.x + NTH * k;
+            if (e >= C * 16) continue;
+            const int i = e >> 4, n4 = e & 15;
+            float4 v = s_red[i * 16 + n4];
+#pragma unroll
+            for (int wv = 1; wv < NWV; ++wv) {
+                const float4 u = s_red[(wv * CP + i) * 16 + n4];
+                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+            }
+            const int p4 = px0 + 4 * n4;
+            const size_t off = ((size_t)b * C + i) * HW + p4;
+            if (p4 + 3 < HW) {
+                if constexpr (ACT) {
+                    const float4 gg = gp_cur[k];
+                    v.x *= gg.x; v.y *= gg.y; v.z *= gg.z; v.w *= gg.w;
+                }
+                cfd_st4u(ga + off, v);
+            } else {
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+                const float gvv[4] = {gp_cur[k].x, gp_cur[k].y, gp_cur[k].z, gp_cur[k].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (p4 + j < HW) {
+                        float x = vv[j];
+                        if constexpr (ACT) x *= gvv[j];
+                        ga[off + j] = x;
+                    }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NST; ++k) gp_cur[k] = gp_next[k];
+        t0 = t1;
+        t1 = t2;
+        __syncthreads();
+    }
+    // ---- this block's partial parameter gradients: [gw1 128*C | gb1 128 | gw2 Co*128 | gb2 Co] (block-major, as k_head_bwd) ----
+    const int o_gb1 = HEAD_HD * C, o_gw2 = o_gb1 + HEAD_HD, o_gb2 = o_gw2 + Co * HEAD_HD;
+    float* dst = part + (size_t)blockIdx.x * (head_part_floats_dev(C, Co));
+#pragma unroll
+    for (int t = 0; t < HT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int jh = HPW * wave + 16 * t + 4 * q + r;
+#pragma unroll
+            for (int v = 0; v < MU; ++v) {
+                const int i = 16 * v + n;
+                if (i < C) dst[(size_t)(jh * C + i)] = aw1[t][v][r];
+            }
+            float s1 = accb1[t][r >> 1][r & 1];  // sums over the 16 pixel lanes of this q group
+#pragma unroll
+            for (int m = 1; m <= 8; m <<= 1) s1 += cfd_shfl_xor(s1, m);
+            if (n == 0) dst[(size_t)(o_gb1 + jh)] = s1;
+#pragma unroll
+            for (int c = 0; c < NCO; ++c) {
+                float sa = acc2[c][t][r >> 1][r & 1];
+#pragma unroll
+                for (int m = 1; m <= 8; m <<= 1) sa += cfd_shfl_xor(sa, m);
+                if (n == 0 && c < Co) dst[(size_t)(o_gw2 + c * HEAD_HD + jh)] = sa;
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {  // the wave that staged a slot's upstream gradients summed them (tiles past the end: zeros)
+        const float s = cfd_wave_sum(gb2a[k]);
+        if (lane == 0 && wave + 4 * k < Co) dst[(size_t)(o_gb2 + wave + 4 * k)] = s;
+    }
+}
+
 // Sum of the per-block partial records part[block][PSTR] (block-major): workgroup = 16 consecutive elements (cfd_record_sum16: every
 // load instruction reads 64-byte runs, fixed summation order, deterministic).
 __global__ __launch_bounds__(256) void k_head_reduce(const HeadTail t) {
@@ -1028,6 +1615,8 @@ extern "C" int cfd_fno_head_bwd(const float* a, const float* mask, const float* 
     CFD_TRY(head_check("cfd_fno_head_bwd", B, C, Hd, Co, HW));
     CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_head_bwd: empty batch");
     hipStream_t st = (hipStream_t)stream;
+    if (Co > 2)  // channel route
+        return head_bwd_co(a, mask, label, preds, gpreds_ext, coef, w1, b1, w2, ga, gw1, gb1, gw2, gb2, ws, B, C, Co, HW, act_in, st);
     const int blocks = head_bwd_blocks(B, HW);
     float* part = (float*)ws;
     const bool v4 = HW % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)ga % 16) == 0;
@@ -1099,6 +1688,12 @@ int cfd_int_fno_head_train_f(const void* a, const float* mask, const float* labe
     CFD_TRY(head_check("cfd_fno_head_train", B, C, Hd, Co, HW));
     CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_head_train: empty batch");
     hipStream_t st = (hipStream_t)stream;
+    if (Co > 2) {  // channel route: forward (sums[0..1]) and backward as two passes, like the wide route; nothing is deferred
+        CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_head_train: bf16 activation storage needs out_chan <= 2 (out_chan=%d)", Co);
+        CFD_REQUIRE(coef && !defer, CFD_ERR_INVALID_ARG, "cfd_fno_head_train: out_chan=%d takes the loss coefficients from memory and defers nothing", Co);
+        CFD_TRY(head_fwd_co((const float*)a, mask, label, w1, b1, w2, b2, preds, sums, ws, B, C, Co, HW, act_in, st, false));
+        return head_bwd_co((const float*)a, mask, label, preds, nullptr, coef, w1, b1, w2, ga, gw1, gb1, gw2, gb2, ws, B, C, Co, HW, act_in, st);
+    }
     const int blocks = head_bwd_blocks(B, HW);
     float* part = (float*)ws;
     const bool v4 = HW % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)ga % 16) == 0 && ((uintptr_t)preds % 16) == 0;
@@ -1154,5 +1749,66 @@ int cfd_int_fno_head_train_f(const void* a, const float* mask, const float* labe
     CFD_PROF_W("k_head_reduce", st, 0.0, 0.0);
     hipLaunchKernelGGL(k_head_reduce, dim3((ht.PS + 15) / 16), dim3(256), 0, st, ht);
     CFD_LAUNCH_CHECK("cfd_fno_head_train(reduce)");
+    return CFD_OK;
+}
+
+// ---- launchers of the channel route (out_chan 3 .. 8, hidden <= 32, fp32 activations) ----
+static int head_fwd_co(const float* a, const float* mask, const float* label, const float* w1, const float* b1, const float* w2,
+                       const float* b2, float* preds, float* sums, void* ws, int B, int C, int Co, int HW, int act_in, hipStream_t st,
+                       bool all_sums) {
+    const int blocks = head_blocks(B, HW, true, C);
+    float* part = label ? (float*)ws : nullptr;
+    {
+    CFD_PROF_W("k_head_fwd_co", st, B * HW * (4.0 * C + 4.0 * (1 + (label ? 2 : 1) * Co)), 2.0 * B * HW * (double)HEAD_HD * (C + Co));
+#define CFD_HFC(Q_, A_, N_) \
+    hipLaunchKernelGGL((k_head_fwd_co<Q_, A_, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW)
+#define CFD_HFC_Q(Q_)                                                                  \
+    do {                                                                               \
+        if (Co <= 4) { if (act_in) CFD_HFC(Q_, true, 4); else CFD_HFC(Q_, false, 4); } \
+        else { if (act_in) CFD_HFC(Q_, true, 8); else CFD_HFC(Q_, false, 8); }         \
+    } while (0)
+    if (C <= 8) CFD_HFC_Q(2);
+    else if (C <= 20) CFD_HFC_Q(5);
+    else CFD_HFC_Q(8);
+#undef CFD_HFC_Q
+#undef CFD_HFC
+    }
+    CFD_LAUNCH_CHECK("cfd_fno_head_fwd(channels)");
+    if (label) {
+        if (all_sums)
+            hipLaunchKernelGGL(k_head_loss_final, dim3(1), dim3(64), 0, st, (const float*)part, blocks, (float)((double)B * Co * HW), sums);
+        else
+            hipLaunchKernelGGL(k_head_loss_final01, dim3(1), dim3(64), 0, st, (const float*)part, blocks, sums);
+        CFD_LAUNCH_CHECK("cfd_fno_head_fwd(channels, loss)");
+    }
+    return CFD_OK;
+}
+
+static int head_bwd_co(const float* a, const float* mask, const float* label, const float* preds, const float* gext, const float* coef,
+                       const float* w1, const float* b1, const float* w2, float* ga, float* gw1, float* gb1, float* gw2, float* gb2,
+                       void* ws, int B, int C, int Co, int HW, int act_in, hipStream_t st) {
+    const int blocks = head_bwd_blocks(B, HW);
+    float* part = (float*)ws;
+    {
+    CFD_PROF_W("k_head_bwd_co", st, 4.0 * B * HW * (2.0 * C + 1 + 2.0 * Co), 2.0 * B * HW * (double)HEAD_HD * (3.0 * C + 2.0 * Co));
+#define CFD_HBC(K_, A_, N_)                                                                                                            \
+    hipLaunchKernelGGL((k_head_bwd_co<K_, A_, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, preds, gext, coef, w1, b1, w2, ga, part, B, \
+                       C, Co, HW)
+#define CFD_HBC_K(K_)                                                                  \
+    do {                                                                               \
+        if (Co <= 4) { if (act_in) CFD_HBC(K_, true, 4); else CFD_HBC(K_, false, 4); } \
+        else { if (act_in) CFD_HBC(K_, true, 8); else CFD_HBC(K_, false, 8); }         \
+    } while (0)
+    if (C <= 8) CFD_HBC_K(2);
+    else if (C <= 20) CFD_HBC_K(5);
+    else CFD_HBC_K(8);
+#undef CFD_HBC_K
+#undef CFD_HBC
+    }
+    CFD_LAUNCH_CHECK("cfd_fno_head_bwd(channels)");
+    const HeadTail ht = cfd_int_head_tail(part, gw1, gb1, gw2, gb2, nullptr, B, C, Co, HW, 0.f);
+    CFD_PROF_W("k_head_reduce", st, 0.0, 0.0);
+    hipLaunchKernelGGL(k_head_reduce, dim3((ht.PS + 15) / 16), dim3(256), 0, st, ht);
+    CFD_LAUNCH_CHECK("cfd_fno_head_bwd(channels, reduce)");
     return CFD_OK;
 }

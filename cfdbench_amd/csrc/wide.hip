@@ -184,10 +184,10 @@ __global__ __launch_bounds__(256) void k_wide_stem(const float* __restrict__ inp
 }
 
 // ---- projection head -------------------------------------------------------------------------------------------------------
-// preds[b][k][p] = mask * (b2[k] + sum_j w2[k][j] gelu(b1[j] + sum_c w1[j][c] f(a[b][c][p]))), k < Co <= 2; lane = pixel with
+// preds[b][k][p] = mask * (b2[k] + sum_j w2[k][j] gelu(b1[j] + sum_c w1[j][c] f(a[b][c][p]))), k < Co <= NCO (2, or 8 for out_chan 3 .. 8); lane = pixel with
 // its CMAX input channels in registers, the 128 hidden units in a rolled loop (weights uniform over the wave).  With a label,
 // each workgroup leaves {sum d^2, sum |d|, sum (label*mask)^2} of its pixels (d = preds - label*mask) in part[blockIdx.x].
-template <int CMAX, bool ACT>
+template <int CMAX, bool ACT, int NCO = 2>
 __global__ __launch_bounds__(256) void k_wide_head(const float* __restrict__ a, const float* __restrict__ mask,
                                                    const float* __restrict__ label, const float* __restrict__ w1,
                                                    const float* __restrict__ b1, const float* __restrict__ w2,
@@ -206,7 +206,9 @@ __global__ __launch_bounds__(256) void k_wide_head(const float* __restrict__ a, 
             if (ACT) v = cfd_gelu(v);
             x[c] = v;
         }
-        float o0 = 0.f, o1 = 0.f;
+        float o[NCO];  // fc2 accumulators, one FMA chain over the hidden units per channel
+#pragma unroll
+        for (int k = 0; k < NCO; ++k) o[k] = 0.f;
         for (int j = 0; j < CFD_HEAD_HD; ++j) {
             const float* wj = w1 + (size_t)j * C;
             float z = b1[j];
@@ -214,12 +216,15 @@ __global__ __launch_bounds__(256) void k_wide_head(const float* __restrict__ a, 
             for (int c = 0; c < CMAX; ++c)
                 if (c < C) z = fmaf(wj[c], x[c], z);
             const float h = cfd_gelu(z);
-            o0 = fmaf(w2[j], h, o0);
-            if (Co > 1) o1 = fmaf(w2[CFD_HEAD_HD + j], h, o1);
+#pragma unroll
+            for (int k = 0; k < NCO; ++k)
+                if (k < Co) o[k] = fmaf(w2[k * CFD_HEAD_HD + j], h, o[k]);
         }
         const float mv = mask ? mask[(size_t)b * HW + p] : 1.f;
-        for (int k = 0; k < Co; ++k) {
-            const float pr = ((k ? o1 : o0) + b2[k]) * mv;
+#pragma unroll
+        for (int k = 0; k < NCO; ++k) {
+            if (k >= Co) break;
+            const float pr = (o[k] + b2[k]) * mv;
             preds[((size_t)b * Co + k) * HW + p] = pr;
             if (label) {
                 const float l = label[((size_t)b * Co + k) * HW + p] * mv;
@@ -255,7 +260,7 @@ __global__ __launch_bounds__(64) void k_wide_loss_final(const float* __restrict_
 // ---- head backward, per pixel ------------------------------------------------------------------------------------------------
 // Lane = pixel of a batch chunk.  Writes h[j] = gelu(z[j]) (hbuf), d loss / d raw output (dout = (gext + coef0 2 d + coef1 sign d)
 // * mask, d = preds - label*mask) and d loss / d z[j] = gelu'(z[j]) sum_k w2[k][j] dout[k] (zbuf, which holds z[j] in between).
-template <int CMAX, bool ACT>
+template <int CMAX, bool ACT, int NCO = 2>
 __global__ __launch_bounds__(256) void k_wide_head_bwd_px(const float* __restrict__ a, const float* __restrict__ mask,
                                                           const float* __restrict__ label, const float* __restrict__ preds,
                                                           const float* __restrict__ gext, const float* __restrict__ coef,
@@ -286,8 +291,12 @@ __global__ __launch_bounds__(256) void k_wide_head_bwd_px(const float* __restric
             hp[(size_t)j * HW] = cfd_gelu(z);
         }
         const float mv = mask ? mask[(size_t)b * HW + p] : 1.f;
-        float d[2] = {0.f, 0.f};
-        for (int k = 0; k < Co; ++k) {
+        float d[NCO];
+#pragma unroll
+        for (int k = 0; k < NCO; ++k) d[k] = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCO; ++k) {
+            if (k >= Co) break;
             const size_t e = ((size_t)b * Co + k) * HW + p;
             float g = gext ? gext[e] : 0.f;
             if (label) {
@@ -299,8 +308,10 @@ __global__ __launch_bounds__(256) void k_wide_head_bwd_px(const float* __restric
             dout[e] = d[k];
         }
         for (int j = 0; j < HD; ++j) {
-            float gh = w2[j] * d[0];
-            if (Co > 1) gh = fmaf(w2[HD + j], d[1], gh);
+            float gh = w2[j] * d[0];  // d/dg = sum_k w2[k][j] dout[k], in channel order
+#pragma unroll
+            for (int k = 1; k < NCO; ++k)
+                if (k < Co) gh = fmaf(w2[k * HD + j], d[k], gh);
             zp[(size_t)j * HW] = gh * cfd_gelu_grad2(cfd_f2{zp[(size_t)j * HW], 0.f}).x;
         }
     }
@@ -506,10 +517,12 @@ int cfd_int_wide_head_bwd(const float* a, const float* mask, const float* label,
         const int nb = B - b0 < bc ? B - b0 : bc;
         const size_t ea = (size_t)b0 * C * HW, eo = (size_t)b0 * Co * HW;
         CFD_PROF_W("k_wide_head_bwd_px", st, 4.0 * nb * HW * (C + 4.0 * CFD_HEAD_HD + 3.0 * Co), 2.0 * nb * HW * (double)CFD_HEAD_HD * (C + Co));
-#define CFD_WHB(CM, A_)                                                                                                                        hipLaunchKernelGGL((k_wide_head_bwd_px<CM, A_>), dim3(grid_blocks((long)nb * HW, 2048)), dim3(256), 0, st, a + ea, mask ? mask + (size_t)b0 * HW : nullptr,                            label ? label + eo : nullptr, preds ? preds + eo : nullptr, gext ? gext + eo : nullptr, coef, w1, b1, w2, zbuf, hbuf, dout, nb, C, Co, HW)
+#define CFD_WHB(CM, A_) do { if (Co <= 2) CFD_WHB_N(CM, A_, 2); else CFD_WHB_N(CM, A_, 8); } while (0)
+#define CFD_WHB_N(CM, A_, N_)                                                                                                                  hipLaunchKernelGGL((k_wide_head_bwd_px<CM, A_, N_>), dim3(grid_blocks((long)nb * HW, 2048)), dim3(256), 0, st, a + ea, mask ? mask + (size_t)b0 * HW : nullptr,                            label ? label + eo : nullptr, preds ? preds + eo : nullptr, gext ? gext + eo : nullptr, coef, w1, b1, w2, zbuf, hbuf, dout, nb, C, Co, HW)
         if (C <= 64) { if (act_in) CFD_WHB(64, true); else CFD_WHB(64, false); }
         else { if (act_in) CFD_WHB(128, true); else CFD_WHB(128, false); }
 #undef CFD_WHB
+#undef CFD_WHB_N
         CFD_LAUNCH_CHECK("cfd_fno_head_bwd(wide px)");
         // d loss / d a = W1^T dz (* gelu'(a) where the head reads GELU(a))
         CFD_TRY(cfd_int_wide_chanmix(zbuf, w1, nullptr, ga + ea, nb, CFD_HEAD_HD, C, HW, 0, 1, stream, act_in ? a + ea : nullptr));
@@ -566,14 +579,16 @@ int cfd_int_wide_head_fwd(const float* a, const float* mask, const float* label,
     const int blocks = grid_blocks((long)B * HW, WIDE_HEAD_BLOCKS);
     float* part = label ? (float*)ws : nullptr;
     CFD_PROF_W("k_wide_head", st, B * HW * (4.0 * C + 4.0 * (1 + (label ? 2 : 1) * Co)), 2.0 * B * HW * (double)CFD_HEAD_HD * (C + Co));
-#define CFD_WH(CM)                                                                                                               \
+#define CFD_WH_N(CM, N_)                                                                                                         \
     do {                                                                                                                         \
-        if (act_in) hipLaunchKernelGGL((k_wide_head<CM, true>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
-        else hipLaunchKernelGGL((k_wide_head<CM, false>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
+        if (act_in) hipLaunchKernelGGL((k_wide_head<CM, true, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
+        else hipLaunchKernelGGL((k_wide_head<CM, false, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
     } while (0)
+#define CFD_WH(CM) do { if (Co <= 2) CFD_WH_N(CM, 2); else CFD_WH_N(CM, 8); } while (0)  // out_chan 3 .. 8: eight accumulators
     if (C <= 64) CFD_WH(64);
     else CFD_WH(128);
 #undef CFD_WH
+#undef CFD_WH_N
     CFD_LAUNCH_CHECK("cfd_fno_head_fwd(wide)");
     if (label) {
         hipLaunchKernelGGL(k_wide_loss_final, dim3(1), dim3(64), 0, st, (const float*)part, blocks, (float)((double)B * Co * HW), sums,

@@ -295,9 +295,10 @@ class FnoTrainEngine:
         # launch).  Data-parallel steps keep them: a rank's gradients must be final and normalised by ITS labels before the all-reduce.
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
         self.defer_flags = 0 if (self.sync.exchange or not fused_head) else 7
-        # the wide-channel route (hidden > 32) and the many-modes route (modes1 > 15 or modes2 > 16) have none of the fused kernels and
-        # ignore the flags (fno.cpp: deferred()): their gradients are final after the pass
-        self._route_defers = self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
+        # the wide-channel route (hidden > 32), the many-modes route (modes1 > 15 or modes2 > 16) and the head's channel route
+        # (out_chan > 2) have none of the fused kernels and ignore the flags (fno.cpp: deferred()): their gradients are final after the pass
+        self._route_defers = (self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
+                              and self.cfg["out_chan"] <= 2)
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.scores_buf = torch.zeros(4, dtype=torch.float32, device=self.device)

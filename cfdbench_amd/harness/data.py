@@ -17,12 +17,17 @@ from torch.utils.data import Dataset
 class SyntheticAutoDataset(Dataset):
     """Smooth random velocity fields advected by a fixed linear map: learnable, deterministic, no files.
 
-    all_features: list over cases of (T, 3, h, w) float32 arrays [u, v, mask]; case_params: list of dicts in the
+    all_features: list over cases of (T, n_fields + 1, h, w) float32 arrays [u, v, (further fields,) mask]; case_params: list of dicts in the
     reference's key order (vel_top, density, viscosity, height, width) -- the attributes test_multistep.py:195-212 reads."""
 
     def __init__(self, n_cases: int = 4, n_frames: int = 6, height: int = 64, width: int = 64, seed: int = 0,
-                 border_mask: bool = False):
+                 border_mask: bool = False, n_fields: int = 2):
+        """n_fields > 2 (a pressure, a temperature, ...) appends further smooth fields of the same kind in front of the mask.  Their
+        amplitudes come from a stream of their own, so u and v are the same arrays whatever n_fields is."""
+        if n_fields < 1:
+            raise ValueError("n_fields must be at least 1")
         rng = np.random.default_rng(seed)
+        rng_extra = np.random.default_rng([seed, 0x6669656c])
         yy, xx = np.meshgrid(np.linspace(0, 1, height), np.linspace(0, 1, width), indexing="ij")
         self.all_features: List[np.ndarray] = []
         self.case_params: List[Dict[str, float]] = []
@@ -32,12 +37,16 @@ class SyntheticAutoDataset(Dataset):
         for _ in range(n_cases):
             vel, dens, visc = rng.uniform(0.5, 1.5), rng.uniform(0.5, 1.5), rng.uniform(0.5, 1.5)
             amp = rng.standard_normal((2, 3, 3)) / (1.0 + np.arange(3)[None, :, None] + np.arange(3)[None, None, :])
+            amp_x = rng_extra.standard_normal((max(n_fields - 2, 0), 3, 3)) / (1.0 + np.arange(3)[None, :, None] + np.arange(3)[None, None, :])
             frames = []
             for t in range(n_frames):
                 ph = 0.15 * t * vel
                 u = sum(amp[0, k, l] * np.sin(2 * np.pi * (k * xx + l * yy) + ph) for k in range(3) for l in range(3))
                 v = sum(amp[1, k, l] * np.cos(2 * np.pi * (k * xx - l * yy) + ph * dens) for k in range(3) for l in range(3))
-                frames.append(np.stack([u * mask, v * mask, mask]).astype(np.float32))
+                extra = [sum(amp_x[f, k, l] * np.sin(2 * np.pi * (k * xx + l * yy) + ph * visc + 0.7 * (f + 1)) for k in range(3) for l in range(3))
+                         for f in range(n_fields - 2)]
+                fields = [u, v][:n_fields] + extra
+                frames.append(np.stack([f * mask for f in fields] + [mask]).astype(np.float32))
             self.all_features.append(np.stack(frames))
             self.case_params.append(dict(vel_top=float(vel), density=float(dens), viscosity=float(visc),
                                          height=1.0, width=1.0))

@@ -154,7 +154,8 @@ int cfd_fno_stem_bwd(const cfd_plan* plan, const float* g, const float* inputs, 
 /* Projection head + mask + MseLoss sums (fno2d.py:228-237, src/models/loss.py:22-37):
  *   preds[b,c,p] = mask[b,p] * (b2[c] + sum_j w2[c,j] gelu(b1[j] + sum_i w1[j,i] f(a[b,i,p])))
  *   if label: sums[0..3] = { sum (preds - label*mask)^2, sum |preds - label*mask|, sum (label*mask)^2, count }
- * a: (B,C,HW); w1: (Hd,C); w2: (Co,Hd); Hd multiple of 16, <= 128; Co <= 2.  label/sums/ws may be NULL together. */
+ * a: (B,C,HW); w1: (Hd,C); w2: (Co,Hd); Hd multiple of 16, <= 128; Co <= 8 (3 .. 8: the channel
+ * route, fp32 activation storage only).  label/sums/ws may be NULL together. */
 size_t cfd_fno_head_workspace_bytes(int B, int C, int Hd, int Co, int HW);
 int cfd_fno_head_fwd(const float* a, const float* mask, const float* label, const float* w1, const float* b1,
                      const float* w2, const float* b2, float* preds, float* sums, void* ws, int B, int C, int Hd,
