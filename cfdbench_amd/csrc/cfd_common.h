@@ -20,6 +20,10 @@ int cfd_tune_get(int which);
         }                                 \
     } while (0)
 
+// include/cfdbench_amd.h, "Alignment": a pointer less aligned than the entry point takes is refused before anything is launched
+#define CFD_REQUIRE_ALIGNED(ptr, bytes, fn, name) \
+    CFD_REQUIRE(((size_t)(ptr) & (size_t)((bytes) - 1)) == 0, CFD_ERR_UNSUPPORTED, "%s: %s must be %d-byte aligned", fn, name, (int)(bytes))
+
 #define CFD_LAUNCH_CHECK(name)                                                        \
     do {                                                                              \
         hipError_t e_ = hipGetLastError();                                            \

@@ -224,9 +224,11 @@ extern "C" int cfd_conv2d_wprep_batch(int n, const float* const* w, void* const*
     CFD_REQUIRE(n >= 0, CFD_ERR_INVALID_ARG, "cfd_conv2d_wprep_batch: negative count");
     if (n == 0) return CFD_OK;
     CFD_REQUIRE(w && wfrag && Ci && Co && ks && transposed, CFD_ERR_INVALID_ARG, "cfd_conv2d_wprep_batch: NULL table");
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         CFD_REQUIRE(cfd_conv2d_wfrag_bytes(Ci[i], Co[i], ks[i], transposed[i]) > 0, CFD_ERR_UNSUPPORTED,
                     "cfd_conv2d_wprep_batch: item %d (%d -> %d channels, kernel size %d) has no fragment form", i, Ci[i], Co[i], ks[i]);
+        CFD_REQUIRE_ALIGNED(wfrag[i], 16, "cfd_conv2d_wprep_batch", "wfrag[i]");
+    }
     CFD_PROF_W("k_conv_wprep", (hipStream_t)stream, 0.0, 0.0);  // (an implementation detail of the k = 3 / 7 kernels: no algorithmic bytes)
     return cfd_conv6_wprep_batch(n, w, wfrag, Ci, Co, ks, transposed, (hipStream_t)stream, "cfd_conv2d_wprep_batch");
 }
@@ -243,7 +245,9 @@ extern "C" int cfd_conv2d_fwd_ex(const float* in, const float* w, const float* b
         CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_conv2d_fwd: statistics of an empty batch");
         CFD_REQUIRE(cfd_conv2d_fwd_stats_slots(B, Ci, Co, H, W, ks) > 0, CFD_ERR_UNSUPPORTED,
                     "cfd_conv2d_fwd: this layer emits no statistics (cfd_conv2d_fwd_stats_slots() == 0)");
+        CFD_REQUIRE_ALIGNED(stats, 16, "cfd_conv2d_fwd", "stats");  // (a record (m, m2, n, -) is written and read as one 16-byte unit)
     }
+    if (wfrag) CFD_REQUIRE_ALIGNED(wfrag, 16, "cfd_conv2d_fwd", "wfrag");  // (fragments are 16-byte units)
     if (B == 0) return CFD_OK;
     const ConvGeom g{B, Ci, Co, H, W, ks};
     CFD_PROF_W("k_conv_fwd", (hipStream_t)stream, 4.0 * ((double)B * (Ci + Co) * H * W + (double)Co * Ci * ks * ks),
@@ -596,6 +600,7 @@ extern "C" int cfd_conv2d_bwd_ex(const float* gout, const float* in, const float
     CFD_REQUIRE(gout && in && w && ws, CFD_ERR_INVALID_ARG, "cfd_conv2d_bwd: NULL pointer");
     CFD_TRY(conv_check("cfd_conv2d_bwd", B, Ci, Co, H, W, ks));
     CFD_REQUIRE(B >= 1, CFD_ERR_INVALID_ARG, "cfd_conv2d_bwd: empty batch");
+    if (wfrag_t) CFD_REQUIRE_ALIGNED(wfrag_t, 16, "cfd_conv2d_bwd", "wfrag_t");
     hipStream_t st = (hipStream_t)stream;
     const ConvGeom g{B, Ci, Co, H, W, ks};
     const int HW = H * W, pad = ks / 2;
@@ -1070,6 +1075,7 @@ extern "C" int cfd_batchnorm_fwd_stats(const float* x, const float* gamma, const
     CFD_REQUIRE(x && gamma && beta && y && save_mean && save_rstd && stats, CFD_ERR_INVALID_ARG, "cfd_batchnorm_fwd_stats: NULL pointer");
     CFD_REQUIRE(B >= 1 && C >= 1 && HW >= 1 && slots >= 1, CFD_ERR_INVALID_ARG, "cfd_batchnorm_fwd_stats: bad sizes");
     CFD_REQUIRE_I31((long)B * C * HW, "cfd_batchnorm_fwd_stats");
+    CFD_REQUIRE_ALIGNED(stats, 16, "cfd_batchnorm_fwd_stats", "stats");  // (bn_slot_stats reads a record as one 16-byte unit)
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W("k_bn_apply", st, 8.0 * B * C * HW, 2.0 * B * C * HW);
     hipLaunchKernelGGL(k_bn_apply, dim3(C, bn_slices(B, C, HW)), dim3(256), 0, st, x, stats, gamma, beta, run_mean, run_var,
@@ -1426,7 +1432,7 @@ extern "C" int cfd_convt2_fwd(const float* in, const float* w, const float* bias
                               int W, void* stream) {
     CFD_REQUIRE(in && w && out, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd: NULL pointer");
     CFD_REQUIRE(B >= 0 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd: bad sizes");
-    CFD_REQUIRE(((size_t)out & 7) == 0, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd: out must be 8-byte aligned (pixel pairs are stored as one vector)");
+    CFD_REQUIRE_ALIGNED(out, 8, "cfd_convt2_fwd", "out");  // (pixel pairs are stored as one vector)
     if (B == 0) return CFD_OK;
     CFD_PROF_W("k_convt2_fwd", (hipStream_t)stream, 4.0 * B * H * W * ((double)Ci + 4.0 * Co), 8.0 * B * H * W * (double)Ci * Co);
     CFD_REQUIRE_I31((long)B * Co * 4 * H * W, "cfd_convt2_fwd");
@@ -1459,7 +1465,7 @@ extern "C" int cfd_convt2_bwd(const float* gout, const float* in, const float* w
                               int B, int Ci, int Co, int H, int W, void* stream) {
     CFD_REQUIRE(gout && in && w && ws, CFD_ERR_INVALID_ARG, "cfd_convt2_bwd: NULL pointer");
     CFD_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, CFD_ERR_INVALID_ARG, "cfd_convt2_bwd: bad sizes");
-    CFD_REQUIRE(((size_t)gout & 7) == 0, CFD_ERR_INVALID_ARG, "cfd_convt2_bwd: gout must be 8-byte aligned (pixel pairs are loaded as one vector)");
+    CFD_REQUIRE_ALIGNED(gout, 8, "cfd_convt2_bwd", "gout");  // (pixel pairs are loaded as one vector)
     CFD_REQUIRE_I31((long)B * (Ci > 4 * Co ? Ci : 4 * Co) * H * W, "cfd_convt2_bwd");
     hipStream_t st = (hipStream_t)stream;
     if (gin) {
@@ -1511,7 +1517,8 @@ extern "C" int cfd_convt2_fwd_ex(const float* in, const float* w, const float* b
     if (out_bstride == 0 || out_bstride == (long)Co * 4 * H * W) return cfd_convt2_fwd(in, w, bias, out, B, Ci, Co, H, W, stream);
     CFD_REQUIRE(in && w && out, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd_ex: NULL pointer");
     CFD_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd_ex: bad sizes");
-    CFD_REQUIRE(((size_t)out & 7) == 0 && out_bstride % 2 == 0, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd_ex: out must be 8-byte aligned");
+    CFD_REQUIRE(out_bstride % 2 == 0, CFD_ERR_INVALID_ARG, "cfd_convt2_fwd_ex: out_bstride must be even (pixel pairs are stored as one vector)");
+    CFD_REQUIRE_ALIGNED(out, 8, "cfd_convt2_fwd_ex", "out");
     CFD_REQUIRE(cfd_tune_get(CFD_TUNE_CONVT_MFMA) != 0 && cfd_convt6_covers(B, Ci, Co, H, W, out_bstride), CFD_ERR_UNSUPPORTED,
                 "cfd_convt2_fwd_ex: a strided output needs the matrix-pipe kernel, which does not take this shape");
     CFD_PROF_W("k_convt2_fwd", (hipStream_t)stream, 4.0 * B * H * W * ((double)Ci + 4.0 * Co), 8.0 * B * H * W * (double)Ci * Co);
@@ -1524,9 +1531,12 @@ extern "C" int cfd_convt2_bwd_ex(const float* gout, long gout_bstride, const flo
     CFD_REQUIRE(gout && in && w && ws, CFD_ERR_INVALID_ARG, "cfd_convt2_bwd_ex: NULL pointer");
     CFD_REQUIRE(B >= 1 && Ci >= 1 && Co >= 1 && H >= 1 && W >= 1, CFD_ERR_INVALID_ARG, "cfd_convt2_bwd_ex: bad sizes");
     CFD_REQUIRE(!gb || gw, CFD_ERR_UNSUPPORTED, "cfd_convt2_bwd_ex: the bias gradient rides in the weight-gradient launches (ask for both)");
-    const bool ok = cfd_tune_get(CFD_TUNE_CONVT_MFMA) != 0 && cfd_convt6_covers(B, Ci, Co, H, W, gout_bstride) && !((size_t)gout & 15) &&
-                    gout_bstride % 4 == 0 && (!gin || !((size_t)w & 15)) && (!gw || (cfd_convt6_wgrad_covers(B, Ci, Co, H, W) && !((size_t)in & 15)));
+    const bool ok = cfd_tune_get(CFD_TUNE_CONVT_MFMA) != 0 && cfd_convt6_covers(B, Ci, Co, H, W, gout_bstride) && gout_bstride % 4 == 0 &&
+                    (!gw || cfd_convt6_wgrad_covers(B, Ci, Co, H, W));
     CFD_REQUIRE(ok, CFD_ERR_UNSUPPORTED, "cfd_convt2_bwd_ex: a strided gradient needs the matrix-pipe kernels, which do not take this shape");
+    CFD_REQUIRE_ALIGNED(gout, 16, "cfd_convt2_bwd_ex", "gout");  // (the matrix-pipe kernels read 16-byte units and have no other form)
+    if (gin) CFD_REQUIRE_ALIGNED(w, 16, "cfd_convt2_bwd_ex", "w");
+    if (gw) CFD_REQUIRE_ALIGNED(in, 16, "cfd_convt2_bwd_ex", "in");
     hipStream_t st = (hipStream_t)stream;
     if (gin) {
         CFD_PROF_W("k_convt2_bwd_in", st, 4.0 * B * H * W * ((double)Ci + 4.0 * Co), 8.0 * B * H * W * (double)Ci * Co);

@@ -1457,8 +1457,10 @@ static int launch_dropout_gelu(const float* x, const float* gy, float* out, size
                                hipStream_t st, const char* what) {
     CFD_REQUIRE(x && out && (!bwd || gy), CFD_ERR_INVALID_ARG, "%s: NULL pointer", what);
     CFD_REQUIRE(p >= 0.f && p < 1.f, CFD_ERR_INVALID_ARG, "%s: p must be in [0, 1)", what);
-    CFD_REQUIRE(n % 4 == 0 && !(((size_t)x | (size_t)out | (size_t)gy) & 15), CFD_ERR_UNSUPPORTED,
-                "%s: needs a multiple of four elements and 16-byte aligned tensors (use cfd_dropout + cfd_gelu_* otherwise)", what);
+    CFD_REQUIRE(n % 4 == 0, CFD_ERR_UNSUPPORTED, "%s: needs a multiple of four elements (use cfd_dropout + cfd_gelu_* otherwise)", what);
+    CFD_REQUIRE_ALIGNED(x, 16, what, "x");  // (16-byte units and no scalar form: cfd_dropout + cfd_gelu_* take any placement)
+    CFD_REQUIRE_ALIGNED(gy, 16, what, "gy");
+    CFD_REQUIRE_ALIGNED(out, 16, what, bwd ? "gx" : "y");
     if (n == 0) return CFD_OK;
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;

@@ -29,6 +29,12 @@ def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
     return t.contiguous()
 
 
+def _aligned(t: Optional[Tensor], nbytes: int) -> Optional[Tensor]:
+    """``t``, or a copy in a fresh allocation where a view's storage offset leaves it off an ``nbytes`` boundary -- for the few arguments
+    the C ABI takes at that alignment only (include/cfdbench_amd.h, "Alignment")."""
+    return t if t is None or t.data_ptr() % nbytes == 0 else t.clone()
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -1100,7 +1106,7 @@ class ConvTranspose2x2Fn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         B, Ci, H, W = x.shape
         Co = w.shape[1]
-        g = _f32c(g)
+        g = _aligned(_f32c(g), 8)  # (pixel pairs are read as one vector)
         gin = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w)
         gb = torch.empty(Co, dtype=torch.float32, device=g.device) if ctx.has_b else None
@@ -1121,7 +1127,8 @@ class ConvTransposeCatFn(torch.autograd.Function):
         B, Ci, H, W = x.shape
         return (x.is_cuda and skip.is_cuda and skip.dtype == torch.float32 and x.dtype == torch.float32 and w.dtype == torch.float32
                 and tuple(skip.shape[2:]) == (2 * H, 2 * W) and skip.shape[0] == B and W % 4 == 0 and (H * W) % 8 == 0
-                and w.data_ptr() % 16 == 0 and w.is_contiguous() and os.environ.get("CFD_CONVT_MFMA", "1") != "0")
+                and w.data_ptr() % 16 == 0 and w.is_contiguous() and (x.data_ptr() % 16 == 0 or not x.is_contiguous())  # (a copy is aligned)
+                and os.environ.get("CFD_CONVT_MFMA", "1") != "0")
 
     @staticmethod
     def forward(ctx, x: Tensor, w: Tensor, b: Optional[Tensor], skip: Tensor):
@@ -1146,7 +1153,7 @@ class ConvTransposeCatFn(torch.autograd.Function):
         has_b, C2 = ctx.meta
         B, Ci, H, W = x.shape
         Co = w.shape[1]
-        g = _f32c(g)
+        g = _aligned(_f32c(g), 16)  # (the slice starts a multiple of 16 bytes into it: H W % 8 == 0)
         plane = 4 * H * W
         gin = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w)

@@ -17,6 +17,21 @@
  *     (tests/backends.py allocates accordingly: poisoned outputs and workspaces between guard bands);
  *   - fp32 tensors are NCHW-contiguous; complex64 tensors are interleaved (re,im) float pairs, exactly
  *     torch.view_as_real of the reference's parameters (state_dict ABI);
+ *   - Alignment.  fp32 tensor arguments (inputs, outputs, parameters, gradients, the flat training buffers and the tensors that
+ *     cfd_fno_params points into them) may sit on any 4-byte boundary, complex64 tensors and 8-byte integers on any 8-byte boundary
+ *     (so a flat buffer that holds complex tensors at even element offsets sits on an 8-byte boundary itself): a contiguous view at
+ *     a storage offset is a valid argument.  The launchers pick the 16- or 8-byte vector form of a kernel only
+ *     when every pointer it applies to has that alignment (and the row length divides), so the placement changes the route and, by
+ *     fp32 summation order, possibly the last bits -- never the function.  Workspaces (void* ws), the statistics records
+ *     (C, slots, 4) of cfd_conv2d_fwd_stats / cfd_batchnorm_fwd_stats and prepared weight fragments (cfd_conv2d_wprep_batch) are
+ *     16-byte units and need 16-byte alignment.  No tensor argument has 2-byte elements: the bf16 activation storage of the _ex
+ *     forms (act_dtype) lives inside the workspace and shares its 16-byte alignment.  The entry points that take a tensor at a coarser alignment only say so where they
+ *     are declared: cfd_convt2_* (8 bytes: out / gout), cfd_convt2_bwd_ex (16 bytes: gout, in, w) and cfd_dropout_gelu_* (16 bytes).
+ *     Such an entry point returns CFD_ERR_UNSUPPORTED -- the one status of a placement it does not take: the arguments are valid and
+ *     another route serves them (a copy in a fresh allocation, or the unfused calls) -- before it launches anything, writes
+ *     nothing, and cfd_last_error() names the argument ("<fn>: <argument> must be N-byte aligned").  No entry point makes a
+ *     16- or 8-byte access to a pointer this paragraph allows to be less aligned (tests/align_checks.py runs every entry point
+ *     on shifted buffers, on a CPU build with -fsanitize=alignment and on the GPU);
  *   - functions are re-entrant; a cfd_plan is immutable after creation and may be shared between threads;
  *   - numerics: fp32 storage and accumulation everywhere.  On 64-wide grids the DFT / inverse-DFT contractions, the
  *     1x1-conv weight gradients and the GEMMs of the projection head run as 3-term split-bf16 products on the bf16
@@ -348,7 +363,7 @@ int cfd_rowdot_bwd(const float* g, const float* branch, const float* trunk, floa
  * (unet.py:20-27 ks=3, resnet.py:35-41 ks=7, unet.py:105 ks=1); bias may be NULL.  ws: cfd_conv2d_fwd_workspace_bytes()
  * bytes (weight fragments and split-K partials of the k = 3 / 7 kernels; 0 for other kernel sizes), or NULL: k = 3 / 7 then run
  * on the slower exact-fp32 gather kernel.  Both routes are fp32-exact class (the k = 3 / 7 kernels multiply three-piece bf16
- * operands, six MFMAs per product).  The 2x2 transposed conv needs `out` / `gout` 8-byte aligned.                        */
+ * operands, six MFMAs per product).  The 2x2 transposed conv needs `out` / `gout` 8-byte aligned (else CFD_ERR_UNSUPPORTED).                        */
 size_t cfd_conv2d_fwd_workspace_bytes(int B, int Ci, int Co, int H, int W, int ks);
 int cfd_conv2d_fwd(const float* in, const float* w, const float* bias, float* out, void* ws, int B, int Ci, int Co, int H,
                    int W, int ks, void* stream);
@@ -356,7 +371,8 @@ int cfd_conv2d_fwd(const float* in, const float* w, const float* bias, float* ou
  * Conv2d -> BatchNorm2d): stats (Co, slots, 4) floats = (m, m2, n, -) = mean of out - bias, sum of squared deviations from it and
  * pixel count of each slot (disjoint pixel sets; running-mean updates, so that nothing cancels when |mean| >> std), slots =
  * cfd_conv2d_fwd_stats_slots() (0: this layer cannot emit them).  Consumed by cfd_batchnorm_fwd_stats (one launch instead of the
- * statistics pass + the normalising pass).                                                                               */
+ * statistics pass + the normalising pass).  stats: 16-byte aligned in both calls (a record is one 16-byte unit), else
+ * CFD_ERR_UNSUPPORTED.                                                                                                     */
 int cfd_conv2d_fwd_stats_slots(int B, int Ci, int Co, int H, int W, int ks);
 int cfd_conv2d_fwd_stats(const float* in, const float* w, const float* bias, float* out, void* ws, float* stats, int B, int Ci,
                          int Co, int H, int W, int ks, void* stream);
@@ -367,7 +383,8 @@ int cfd_conv2d_fwd_stats(const float* in, const float* w, const float* bias, flo
  * other than 3 / 7), transposed = 0 for the forward pass, 1 for the input-gradient pass; the form depends on neither batch nor
  * grid size.  The fragments are a pure function of the weights: remake them after every change of the weights (optimizer step,
  * load_state_dict).  cfd_conv2d_fwd_ex / cfd_conv2d_bwd_ex are the calls above with the optional extras spelled out -- stats (NULL
- * or as in cfd_conv2d_fwd_stats) and wfrag / wfrag_t (NULL or the prepared fragments; ignored on layers that run elsewhere).  */
+ * or as in cfd_conv2d_fwd_stats) and wfrag / wfrag_t (NULL or the prepared fragments; ignored on layers that run elsewhere).
+ * Fragment buffers are 16-byte aligned (else CFD_ERR_UNSUPPORTED).  */
 size_t cfd_conv2d_wfrag_bytes(int Ci, int Co, int ks, int transposed);
 int cfd_conv2d_wprep_batch(int n, const float* const* w, void* const* wfrag, const int* Ci, const int* Co, const int* ks,
                            const int* transposed, void* stream);
@@ -425,7 +442,8 @@ int cfd_convt2_bwd(const float* gout, const float* in, const float* w, float* gi
 /* The same with the 2H x 2W tensor addressed as a channel slice of a wider one (out / gout = the slice's first channel of image 0,
  * *_bstride = elements between consecutive images, 0 = dense): unet.py:80-88 concatenates the transposed convolution's output behind
  * the skip tensor -- written there directly and its gradient read from there, a pass over it is saved in each direction.  Strided
- * tensors run on the matrix-pipe kernels only: CFD_ERR_UNSUPPORTED where those do not apply (W % 4, H W % 8, alignment).        */
+ * tensors run on the matrix-pipe kernels only: CFD_ERR_UNSUPPORTED where those do not apply (W % 4, H W % 8).  Alignment: `out` 8 bytes;
+ * cfd_convt2_bwd_ex `gout` 16 bytes, `w` 16 bytes when gin is asked for, `in` 16 bytes when gw is (else CFD_ERR_UNSUPPORTED).        */
 int cfd_convt2_fwd_ex(const float* in, const float* w, const float* bias, float* out, long out_bstride, int B, int Ci, int Co, int H,
                       int W, void* stream);
 int cfd_convt2_bwd_ex(const float* gout, long gout_bstride, const float* in, const float* w, float* gin, float* gw, float* gb, void* ws,

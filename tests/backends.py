@@ -7,9 +7,19 @@ The allocators are hostile on purpose -- the product hands the kernels torch.emp
   zeros(shape, dtype)  a buffer the CONTRACT (include/cfdbench_amd.h) requires the caller to zero, or that carries state in
   dev(array)           an input
 Every buffer is carved out of a larger allocation with GUARD bytes of GUARD_BYTE in front and behind; verify() checks
-all of them byte for byte.  4096 guard bytes keep the inner pointer at the alignment of a plain allocation."""
+all of them byte for byte.  4096 guard bytes keep the inner pointer at the alignment of a plain allocation.
+
+Placement: the payload starts GUARD + shift bytes into its allocation.  The shift is 0 unless a check runs inside
+`with be.misaligned(nbytes, only=None, place=None)`: then dev() / out() / zeros() place their payload `nbytes` past the 16-byte
+boundary (the kernels pick their route from the pointer's alignment, include/cfdbench_amd.h "Alignment"), scratch() never does
+(workspaces are 16-byte aligned by contract).  The shift is rounded up to the element size, so a complex64 / int64 / float64 buffer
+is never placed below its own 8-byte alignment.  `only = k` shifts just the k-th buffer (0-based) allocated since the policy was
+set; `place = {k: nbytes}` gives single buffers (same numbering) a shift of their own -- 0 or 8 for the ones the contract wants
+16- or 8-byte aligned.
+be.allocations counts the dev() / out() / zeros() buffers since the policy was last set (or since the backend was made)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -41,13 +51,53 @@ def _first_damage(band):
 class _Guarded:
     """Bookkeeping common to both backends: the live (whole allocation, payload bytes, description) records."""
 
-    def _track(self, whole, nbytes, what):
-        self._live.append((whole, nbytes, what))
+    allocations = 0
+    _policy = (0, None, {})
+
+    def _track(self, whole, nbytes, what, shift=0):
+        self._live.append((whole, nbytes, what, shift))
+
+    @contextlib.contextmanager
+    def misaligned(self, nbytes, only=None, place=None):
+        """Placement policy for the duration of a check (module docstring): dev() / out() / zeros() payloads at GUARD + nbytes."""
+        place = dict(place or {})
+        assert all(v in (0, 4, 8) for v in [nbytes, *place.values()]) and (only is None or only >= 0), (nbytes, only, place)
+        saved = (self._policy, self.allocations)
+        self._policy, self.allocations = (int(nbytes), only, place), 0
+        try:
+            yield self
+        finally:
+            self._policy, self.allocations = saved
+
+    def _shift(self, dtype, placed):
+        """The shift of the next buffer; `placed` buffers (all but scratch) are counted and obey the policy."""
+        if not placed:
+            return 0
+        k, self.allocations = self.allocations, self.allocations + 1
+        nbytes, only, place = self._policy
+        if only is not None and k != only:
+            return 0
+        nbytes = place.get(k, nbytes)
+        item = np.dtype(dtype).itemsize
+        return -(-nbytes // item) * item  # (never below the element's own alignment: 4 -> 8 for complex64 / int64 / float64)
+
+    def payloads(self, kind="out"):
+        """(device address, description, payload bytes on the host) of every live buffer that `kind`() made since the last verify()."""
+        for whole, n, what, sh in self._live:
+            if what.startswith(kind + " "):
+                yield self.ptr(whole) + GUARD + sh, what, self.host(whole[GUARD + sh:GUARD + sh + n])
+
+    def guard_front(self, buf):
+        """The guard band in front of `buf` (a dev() / out() / zeros() / scratch() buffer not yet verified), as a writable uint8 view."""
+        for whole, n, _, sh in self._live:
+            if self.ptr(whole) + GUARD + sh == self.ptr(buf):
+                return whole[:GUARD + sh]
+        raise KeyError("not a live buffer of this backend")
 
     def _report(self, damaged):
         lines = []
-        for what, side, (off, cnt) in damaged:
-            lines.append(f"{what}: {side} guard band damaged, first at byte {off} of {GUARD}, {cnt} byte(s)")
+        for what, side, (off, cnt), size in damaged:
+            lines.append(f"{what}: {side} guard band damaged, first at byte {off} of {size}, {cnt} byte(s)")
         raise AssertionError("write outside a buffer's declared size:\n  " + "\n  ".join(lines))
 
     def bytes(self, n):
@@ -58,10 +108,11 @@ class NumpyBackend(_Guarded):
     """libcfd_emul.so: the product kernel sources compiled against tests/emul (host threads)."""
     name = "emul"
 
-    def __init__(self):
+    def __init__(self, sanitize=False):
+        """sanitize: the second library of tests/emul/build_emul.py, host code under -fsanitize=alignment."""
         from cfdbench_amd._capi import CApi
         from tests.emul.build_emul import build
-        self.api = CApi(ctypes.CDLL(str(build())))
+        self.api = CApi(ctypes.CDLL(str(build(sanitize=sanitize))))
         self.stream = None
         self._live = []
 
@@ -69,9 +120,11 @@ class NumpyBackend(_Guarded):
         dtype = np.dtype(dtype)
         shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
-        whole = np.full(n + 2 * GUARD, GUARD_BYTE, np.uint8)
-        self._track(whole, n, f"{what} shape={shape} dtype={dtype}")
-        return whole[GUARD:GUARD + n], whole[GUARD:GUARD + n].view(dtype).reshape(shape)
+        sh = self._shift(dtype, what != "scratch")
+        whole = np.full(n + 2 * GUARD + sh, GUARD_BYTE, np.uint8)
+        assert whole.ctypes.data % 16 == 0
+        self._track(whole, n, f"{what} shape={shape} dtype={dtype}" + (f" shift={sh}" if sh else ""), sh)
+        return whole[GUARD + sh:GUARD + sh + n], whole[GUARD + sh:GUARD + sh + n].view(dtype).reshape(shape)
 
     def dev(self, a):
         a = np.ascontiguousarray(a)
@@ -106,11 +159,11 @@ class NumpyBackend(_Guarded):
     def verify(self):
         live, self._live = self._live, []
         damaged = []
-        for whole, n, what in live:
-            for side, band in (("front", whole[:GUARD]), ("back", whole[GUARD + n:])):
+        for whole, n, what, sh in live:
+            for side, band in (("front", whole[:GUARD + sh]), ("back", whole[GUARD + sh + n:])):
                 d = _first_damage(band)
                 if d:
-                    damaged.append((what, side, d))
+                    damaged.append((what, side, d, band.size))
         if damaged:
             self._report(damaged)
 
@@ -136,9 +189,11 @@ class TorchBackend(_Guarded):
         dtype = np.dtype(dtype)
         shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
-        whole = self.torch.full((n + 2 * GUARD,), GUARD_BYTE, dtype=self.torch.uint8, device="cuda")
-        self._track(whole, n, f"{what} shape={shape} dtype={dtype}")
-        raw = whole[GUARD:GUARD + n]
+        sh = self._shift(dtype, what != "scratch")
+        whole = self.torch.full((n + 2 * GUARD + sh,), GUARD_BYTE, dtype=self.torch.uint8, device="cuda")
+        assert whole.data_ptr() % 16 == 0
+        self._track(whole, n, f"{what} shape={shape} dtype={dtype}" + (f" shift={sh}" if sh else ""), sh)
+        raw = whole[GUARD + sh:GUARD + sh + n]
         return raw, raw.view(self._tdtype(dtype)).view(shape)
 
     def _fill_poison(self, raw):
@@ -183,14 +238,14 @@ class TorchBackend(_Guarded):
         if not live:
             return
         self.sync()
-        flags = [(whole[:GUARD] != GUARD_BYTE).any() | (whole[GUARD + n:] != GUARD_BYTE).any() for whole, n, _ in live]
+        flags = [(whole[:GUARD + sh] != GUARD_BYTE).any() | (whole[GUARD + sh + n:] != GUARD_BYTE).any() for whole, n, _, sh in live]
         hit = self.torch.stack(flags).cpu().numpy()
         damaged = []
-        for (whole, n, what), h in zip(live, hit):
+        for (whole, n, what, sh), h in zip(live, hit):
             if h:
-                for side, band in (("front", whole[:GUARD]), ("back", whole[GUARD + n:])):
+                for side, band in (("front", whole[:GUARD + sh]), ("back", whole[GUARD + sh + n:])):
                     d = _first_damage(band.cpu().numpy())
                     if d:
-                        damaged.append((what, side, d))
+                        damaged.append((what, side, d, band.numel()))
         if damaged:
             self._report(damaged)

@@ -1,6 +1,7 @@
 """CPU: the hostile allocators of tests/backends.py bite.  Three deliberately broken stand-ins for a C-ABI entry point (raw pointers and
 sizes, written here, not in the product) -- one leaves an output element unwritten, one adds into its output, one writes 4 bytes past
-its workspace -- pass on friendly zeroed memory and are caught on out() / scratch() / by verify().  Also: every workspace size function
+its workspace -- pass on friendly zeroed memory and are caught on out() / scratch() / by verify(); a fourth writes 4 bytes in front of a
+payload placed off the 16-byte grid (be.misaligned) and is caught there too.  Also: every workspace size function
 of include/cfdbench_amd.h is named by tests/kernel_checks.py: WORKSPACE_COVERAGE."""
 import ctypes
 import inspect
@@ -43,6 +44,11 @@ def twice_overrunning_scratch(x, y, ws, ws_bytes, n):
     """y = 2 x through a workspace, with one float stored just past the workspace's end."""
     _u8(ws, ws_bytes + 4)[ws_bytes:] = 0
     _f32(y, n)[:] = 2.0 * _f32(x, n)
+
+
+def twice_underrunning(x, y, n):
+    """y = 2 x, with one float stored just in front of y (an aligned vector store at an address rounded down)."""
+    _f32(y - 4, n + 1)[:] = np.concatenate([[0.0], 2.0 * _f32(x, n)])
 
 
 def _parity(be, fn, alloc, n=37):
@@ -98,6 +104,44 @@ def test_write_in_front_of_an_input_is_caught(be):
     _u8(be.ptr(dx) - 2, 2)[:] = 7
     with pytest.raises(AssertionError, match=r"dev shape=\(2, 3\) dtype=complex64: front guard band damaged, first at byte 4094 of 4096, 2 byte"):
         be.verify()
+
+
+def test_write_in_front_of_a_shifted_payload_is_caught(be):
+    """The guard bands follow the payload to its place: the front band of a buffer shifted by 4 bytes is 4100 bytes long and ends at it."""
+    n = 9
+    with be.misaligned(4):
+        dx, y = be.dev(np.ones(n, np.float32)), be.out((n,))
+        assert be.allocations == 2
+    assert be.ptr(y) % 16 == 4
+    twice_underrunning(be.ptr(dx), be.ptr(y), n)                               # (lands in the guard band: memory this test allocated)
+    assert K.nm(be.host(y), np.full(n, 2.0)) < K.TOL                           # the results are right; only the guard shows it
+    with pytest.raises(AssertionError) as e:
+        be.verify()
+    msg = str(e.value)
+    assert "out shape=(9,) dtype=float32 shift=4: front guard band damaged, first at byte 4096 of 4100, 4 byte(s)" in msg, msg
+    assert msg.count("guard band damaged") == 1
+
+
+def test_placement_policy(be):
+    """Shift 0 by default and after the policy ends; inside it dev() / out() / zeros() sit `shift` bytes past a 16-byte boundary, 8-byte
+    element types never below 8, scratch() always on the boundary; `only` and `place` single buffers out by their allocation index."""
+    x = np.arange(6, dtype=np.float32)
+    assert [be.ptr(b) % 16 for b in (be.dev(x), be.out((3,)), be.zeros((3,)), be.scratch(5))] == [0, 0, 0, 0]
+    for shift in (4, 8):
+        with be.misaligned(shift):
+            bufs = [be.dev(x), be.out((3,)), be.zeros((3,)), be.out((2,), np.complex64), be.dev(np.array([7], np.int64)), be.scratch(5)]
+            assert [be.ptr(b) % 16 for b in bufs] == [shift, shift, shift, 8, 8, 0]
+            assert be.allocations == 5                                          # (scratch() is not counted)
+            assert np.array_equal(be.host(bufs[0]), x) and not be.host(bufs[2]).any() and int(be.host(bufs[4])[0]) == 7
+            assert (be.host(bufs[1]).view(np.uint32) == BK.POISON_WORD).all() and (be.host(bufs[3]).view(np.uint32) == BK.POISON_WORD).all()
+    with be.misaligned(4, only=1):
+        assert [be.ptr(be.out((3,))) % 16 for _ in range(3)] == [0, 4, 0]
+    with be.misaligned(4, place={0: 0, 2: 8}):
+        assert [be.ptr(be.out((3,))) % 16 for _ in range(3)] == [0, 4, 8]
+    with be.misaligned(0):
+        assert be.ptr(be.out((3,))) % 16 == 0
+    assert be.ptr(be.out((3,))) % 16 == 0
+    be.verify()
 
 
 def test_every_size_function_is_exercised_on_a_guarded_workspace():
