@@ -53,6 +53,7 @@ _SIGS = {
     "cfd_prof_end": (_I, [C.c_char_p, _Z]),
     "cfd_plan_create": (_I, [_I, _I, _I, _I, C.POINTER(_P)]),
     "cfd_plan_destroy": (None, [_P]),
+    "cfd_spectral_transform_lds_bytes": (_I, [_I, _I, _I, _I, _I]),
     "cfd_spectral_dft": (_I, [_P, _P, _P, _I, _I, _P]),
     "cfd_spectral_mix": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfd_spectral_idft": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),

@@ -88,7 +88,7 @@ struct cfd_plan {
     float* d_clhw;  // [m2]  c_l / (H*W)
     float* d_gx;    // [H]  np.linspace(0,1,H) as float32   (fno2d.py:251)
     float* d_gy;    // [W]
-    // Many-modes route (dft_many.hip): every plan with m1 > 15 or m2 > 16.  Such a plan has only the fp32 tables below (d_fwd, d_inv,
+    // Many-modes route (dft_many.hip): every plan with m1 > 15 or m2 > 16 or W > 80.  Such a plan has only the fp32 tables below (d_fwd, d_inv,
     // d_fwd_b3, d_inv_b3, d_fwd_g, d_inv_g, d_tail are NULL), the narrow plans have NULL here.  Dimensions: cfd_many_dims().
     int many;
     float* d_many_fwd;  // T1[Wk][N1p] (column c < m2: cos, m2 <= c < 2 m2: -sin of 2 pi l y / W) | T2C[R2p][Hk] | T2S[R2p][Hk] (cos / sin of

@@ -80,7 +80,15 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     CFD_REQUIRE(s->out_chan <= 2 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: out_chan=%d: bf16 activation storage needs out_chan <= 2", fn,
                 s->out_chan);
     CFD_REQUIRE(!p->many || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED,
-                "%s: modes (%d,%d): bf16 activation storage needs modes1 <= 15 and modes2 <= 16", fn, p->m1, p->m2);
+                "%s: grid %dx%d, modes (%d,%d): bf16 activation storage needs modes1 <= 15, modes2 <= 16 and W <= 80", fn, p->H, p->W, p->m1,
+                p->m2);
+    // Grids wider than 80 columns: the pixel-domain kernels index activations with 32-bit products of at most B * max(hidden, head) * H * W
+    // elements (at 128 x 128 and head width 128: B <= 1023): refuse what would wrap
+    if (p->W > 80) {
+        const long long widest = s->hidden > s->head ? s->hidden : s->head;
+        CFD_REQUIRE((long long)s->B * widest * s->H * s->W <= 0x7fffffffLL, CFD_ERR_UNSUPPORTED,
+                    "%s: B=%d at %dx%d, width %d: more than 2^31 - 1 activation elements per tensor", fn, s->B, s->H, s->W, (int)widest);
+    }
     return CFD_OK;
 }
 

@@ -54,7 +54,7 @@ static double hermitian_scale(int l, int H, int W) {
     return ((l == 0 || (W % 2 == 0 && l == W / 2)) ? 1.0 : 2.0) / ((double)H * W);
 }
 
-// The many-modes plan (m1 > 15 or m2 > 16): fp32 tables of the two GEMM stages of dft_many.hip, built in double precision, zero-padded
+// The many-modes plan (m1 > 15 or m2 > 16 or W > 80): fp32 tables of the two GEMM stages of dft_many.hip, built in double precision, zero-padded
 // to the extents of cfd_many_dims() so that the kernels read whole 16 x 4 / 4 x 16 operand fragments without bounds checks.
 static int cfd_plan_create_many(int H, int W, int m1, int m2, cfd_plan** out) {
     cfd_plan* p = new cfd_plan();
@@ -121,13 +121,14 @@ static int cfd_plan_create_many(int H, int W, int m1, int m2, cfd_plan** out) {
 
 extern "C" int cfd_plan_create(int H, int W, int m1, int m2, cfd_plan** out) {
     CFD_REQUIRE(out != nullptr, CFD_ERR_INVALID_ARG, "cfd_plan_create: out is NULL");
-    CFD_REQUIRE(H >= 2 && H <= 128 && W >= 2 && W <= 80, CFD_ERR_UNSUPPORTED,
-                "cfd_plan_create: grid %dx%d unsupported (need 2<=H<=128, 2<=W<=80)", H, W);
+    CFD_REQUIRE(H >= 2 && H <= 128 && W >= 2 && W <= 128, CFD_ERR_UNSUPPORTED,
+                "cfd_plan_create: grid %dx%d unsupported (need 2<=H<=128, 2<=W<=128)", H, W);
     CFD_REQUIRE(m1 >= 1 && 2 * m1 <= H, CFD_ERR_UNSUPPORTED,
                 "cfd_plan_create: modes1=%d unsupported (need 1<=m1 and 2*m1<=H=%d)", m1, H);
     CFD_REQUIRE(m2 >= 1 && m2 <= W / 2 + 1, CFD_ERR_UNSUPPORTED,
                 "cfd_plan_create: modes2=%d unsupported (need 1<=m2<=W/2+1, W=%d)", m2, W);
-    if (m1 > 15 || m2 > 16) return cfd_plan_create_many(H, W, m1, m2, out);
+    // the narrow route's lane maps end at NJ = 5 column tiles: every wider grid is a many-modes plan, whatever its mode counts
+    if (m1 > 15 || m2 > 16 || W > 80) return cfd_plan_create_many(H, W, m1, m2, out);
     cfd_plan* p = new cfd_plan();
     p->H = H; p->W = W; p->m1 = m1; p->m2 = m2;
     p->NJ = (W + 15) / 16;

@@ -722,8 +722,8 @@ int cfd_int_spectral_dft_stem(const cfd_plan* p, const float* inputs, const floa
 int cfd_int_spectral_dft(const cfd_plan* p, const void* x, float* xh, int nimg, int act_in, int dt, void* stream) {
     if (dt == CFD_DT_F32) return cfd_spectral_dft(p, (const float*)x, xh, nimg, act_in, stream);
     CFD_REQUIRE(p && x && xh && nimg >= 0, CFD_ERR_INVALID_ARG, "cfd_spectral_dft: NULL pointer or negative count");
-    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_dft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
-                p->m1, p->m2);
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_dft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 and W <= 80 (plan: %dx%d, modes %d, %d)",
+                p->H, p->W, p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(act_in ? "k_dft_fwd_act" : "k_dft_fwd", st, (double)nimg * (2.0 * p->H * p->W + 16.0 * p->m1 * p->m2),
@@ -1960,8 +1960,8 @@ int cfd_int_spectral_idft(const cfd_plan* p, const float* z, const void* addend,
     if (dt == CFD_DT_F32) return cfd_spectral_idft(p, z, (const float*)addend, (const float*)aprev, (float*)out, nimg, epi, stream);
     CFD_REQUIRE(p && z && out && nimg >= 0 && epi >= 0 && epi <= 2 && (epi < 1 || addend) && (epi < 2 || aprev), CFD_ERR_INVALID_ARG,
                 "cfd_spectral_idft: bad arguments");
-    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
-                p->m1, p->m2);
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft: bf16 activation storage needs modes m1 <= 15, m2 <= 16 and W <= 80 (plan: %dx%d, modes %d, %d)",
+                p->H, p->W, p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
@@ -1978,8 +1978,8 @@ int cfd_int_spectral_idft_grad(const cfd_plan* p, const float* z, const float* a
     const int epi = aprev ? 2 : 1;
     if (dt == CFD_DT_F32) return cfd_spectral_idft(p, z, addend, (const float*)aprev, out, nimg, epi, stream);
     CFD_REQUIRE(p && z && out && addend && nimg >= 0, CFD_ERR_INVALID_ARG, "cfd_spectral_idft(grad): bad arguments");
-    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft(grad): bf16 activation storage needs modes m1 <= 15, m2 <= 16 (plan: %d, %d)",
-                p->m1, p->m2);
+    CFD_REQUIRE(!p->many, CFD_ERR_UNSUPPORTED, "cfd_spectral_idft(grad): bf16 activation storage needs modes m1 <= 15, m2 <= 16 and W <= 80 (plan: %dx%d, modes %d, %d)",
+                p->H, p->W, p->m1, p->m2);
     if (nimg == 0) return CFD_OK;
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W(epi == 1 ? "k_idft_add" : "k_idft_add_dgelu", st,

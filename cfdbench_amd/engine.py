@@ -295,10 +295,12 @@ class FnoTrainEngine:
         # launch).  Data-parallel steps keep them: a rank's gradients must be final and normalised by ITS labels before the all-reduce.
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
         self.defer_flags = 0 if (self.sync.exchange or not fused_head) else 7
-        # the wide-channel route (hidden > 32), the many-modes route (modes1 > 15 or modes2 > 16) and the head's channel route
-        # (out_chan > 2) have none of the fused kernels and ignore the flags (fno.cpp: deferred()): their gradients are final after the pass
-        self._route_defers = (self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
+        # the wide-channel route (hidden > 32), the many-modes route (modes1 > 15 or modes2 > 16, or a grid wider than 80 columns: known
+        # per batch, _prepare) and the head's channel route (out_chan > 2) have none of the fused kernels and ignore the flags (fno.cpp:
+        # deferred()): their gradients are final after the pass
+        self._model_defers = (self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
                               and self.cfg["out_chan"] <= 2)
+        self._route_defers = self._model_defers
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.scores_buf = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -312,6 +314,7 @@ class FnoTrainEngine:
         if key == self._shape_key:
             return
         c = self.cfg
+        self._route_defers = self._model_defers and W <= 80  # (cfd_plan_create: every plan with W > 80 is a many-modes plan)
         self.plan = _lib.plan(H, W, c["modes1"], c["modes2"], self.device.index)
         self.shape = FnoShape(B, H, W, in_chan, c["out_chan"], case_params.shape[1], c["hidden"], self.L, c["modes1"],
                               c["modes2"], c["head"])

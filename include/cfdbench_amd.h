@@ -81,13 +81,18 @@ int cfd_prof_end(char* buf, size_t cap);
 /* ---- plan: pruned-DFT operator tables for one grid (H,W) and mode count (m1,m2) -------------------------
  * Replaces the implicit FFT plans behind torch.fft.rfft2 / irfft2 (src/models/fno/fno2d.py:62,81) and the
  * per-call host-side np.linspace coordinate grids of Fno2d.get_coords (fno2d.py:244-255).
- * Grids 2 <= H <= 128, 2 <= W <= 80; modes 1 <= m1 with 2*m1 <= H, 1 <= m2 <= W/2+1 (the reference's range, fno2d.py:59-82).
- * m1 <= 15 and m2 <= 16 is the narrow route (spectral.hip); any other plan is a many-modes plan (dft_many.hip): fp32 activation
- * storage only, no FnoBlock / lifting-layer fusion.
+ * Grids 2 <= H <= 128, 2 <= W <= 128; modes 1 <= m1 with 2*m1 <= H, 1 <= m2 <= W/2+1 (the reference's range, fno2d.py:59-82).
+ * m1 <= 15 and m2 <= 16 on a grid with W <= 80 is the narrow route (spectral.hip); any other plan -- more modes, or W > 80 whatever
+ * its modes -- is a many-modes plan (dft_many.hip): fp32 activation storage only, no FnoBlock / lifting-layer fusion.
  * Allocates a few tens of KB of device memory; create once per (H,W,m1,m2), never inside stream capture. */
 typedef struct cfd_plan cfd_plan;
 int cfd_plan_create(int H, int W, int m1, int m2, cfd_plan** out);
 void cfd_plan_destroy(cfd_plan* plan);
+/* Dynamic LDS in bytes that a workgroup of the many-modes transforms asks for at most on the plan (H,W,m1,m2): inverse = 0 the forward
+ * transform, 1 the inverse.  Never above 163840 (the 160 KB of a CU); the launchers use the same figure and refuse with
+ * CFD_ERR_UNSUPPORTED beyond it.  0 for a narrow plan and for arguments cfd_plan_create() refuses.  Needs no device.  The return value is
+ * the byte count, not a status (an int, not a size_t: it is no workspace size a caller has to allocate). */
+int cfd_spectral_transform_lds_bytes(int H, int W, int m1, int m2, int inverse);
 
 /* ---- SpectralConv2d_fast pieces (src/models/fno/fno2d.py:59-82) ----------------------------------------
  * Kept modes: rows K = [0,m1) U [H-m1,H) (2*m1 rows, in that order) x columns [0,m2).  M = 2*m1*m2.        */

@@ -2,8 +2,12 @@
 """Dev tool (GPU box): the FNO at given Fourier mode counts -- the fused training step (FnoTrainEngine) and a whole-horizon rollout
 (FnoRollout) -- with the per-kernel split of one step and each transform's share of its paper bound.
 
-    python tools/bench_modes.py [--modes 16,16 24,24 32,33] [--hidden 20 32] [--batch 256] [--steps 20] [--warmup 5]
-                                [--rollout 16,16] [--rollout-hidden 32] [--rollout-batch 64] [--rollout-steps 200] [--json FILE]
+    python tools/bench_modes.py [--modes 16,16 24,24 32,33] [--hidden 20 32] [--batch 256] [--steps 20] [--warmup 5] [--grid 64,64]
+                                [--rollout 16,16] [--rollout-hidden 32] [--rollout-batch 64] [--rollout-steps 200] [--rollout-grid 66,65]
+                                [--json FILE]
+
+--grid H,W (the step; also --height / --width) and --rollout-grid H,W reach the grids up to 128 x 128, e.g. the large-grid table of LABNOTES:
+    python tools/bench_modes.py --grid 128,128 --batch 64 --modes 12,12 32,33 --rollout 12,12 --rollout-hidden 20 --rollout-grid 128,128
 
 Prints one JSON line per measurement.  The paper bound of a transform launch is the larger of its FLOP at 155 TF (fp32 matrix / vector
 pipe) and its algorithmic bytes at 8 TB/s, both as declared at the launch site (CFD_PROF_W: F = 4 H W m2 + 16 H m1 m2 per image and
@@ -93,7 +97,7 @@ def step_leg(api, args, C, m1, m2, dev):
 
 
 def rollout_leg(args, C, m1, m2, dev):
-    B, H, W, p, steps = args.rollout_batch, 66, 65, 5, args.rollout_steps
+    B, (H, W), p, steps = args.rollout_batch, (int(v) for v in args.rollout_grid.split(",")), 5, args.rollout_steps
     g = torch.Generator(device="cpu").manual_seed(99)
     x0 = torch.randn(B, 2, H, W, generator=g).to(dev)
     cp = torch.randn(B, p, generator=g).to(dev)
@@ -118,6 +122,8 @@ def main():
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--height", type=int, default=64)
     ap.add_argument("--width", type=int, default=64)
+    ap.add_argument("--grid", default="", help="H,W of the step leg (overrides --height / --width)")
+    ap.add_argument("--rollout-grid", default="66,65", help="H,W of the rollout leg")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rollout", nargs="*", default=["16,16"])
@@ -126,6 +132,8 @@ def main():
     ap.add_argument("--rollout-steps", type=int, default=200)
     ap.add_argument("--json", default="")
     args = ap.parse_args()
+    if args.grid:
+        args.height, args.width = (int(v) for v in args.grid.split(","))
     api = _lib.api()
     dev = torch.device("cuda", 0)
     out = []
