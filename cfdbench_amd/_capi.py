@@ -19,7 +19,7 @@ class CfdError(RuntimeError):
 
 class FnoShape(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
-        "B", "H", "W", "in_chan", "out_chan", "n_case_params", "hidden", "num_layers", "modes1", "modes2", "head")]
+        "B", "H", "W", "in_chan", "out_chan", "n_case_params", "hidden", "num_layers", "modes1", "modes2", "head", "pad")]
 
 
 class FnoParams(C.Structure):
@@ -40,7 +40,7 @@ class FfnStackArgs(C.Structure):
 
 
 _P = C.c_void_p
-ABI_VERSION = 601  # include/cfdbench_amd.h: CFD_ABI_VERSION
+ABI_VERSION = 602  # include/cfdbench_amd.h: CFD_ABI_VERSION
 _I = C.c_int
 _F = C.c_float
 _Z = C.c_size_t

@@ -166,6 +166,16 @@ int cfd_int_fno_head_fwd(const void* a, const float* mask, const float* label, c
                          const float* b2, float* preds, float* sums, void* ws, int B, int C, int Hd, int Co, int HW, int act_in,
                          int dt, void* stream);
 
+// Domain padding (pad.hip; cfd_fno_shape.pad > 0, fp32 storage): the lifting layer written into the (H + pad) x (W + pad) layout with a zero
+// band, and the copies between that layout and the compact H x W one.  `coords` (may be NULL): CFD_PAD_COORD_FLOATS floats that receive the
+// DATA grid's coordinate tables, gx[H] at 0 and gy[W] at CFD_PAD_COORD_GY -- what the lifting layer's gradient reads in place of the plan's.
+#define CFD_PAD_COORD_GY 128
+#define CFD_PAD_COORD_FLOATS 256
+int cfd_int_stem_pad(const float* inputs, const float* mask, const float* case_params, const float* w, const float* bias, float* out,
+                     float* coords, int B, int in_chan, int P, int C, int H, int W, int pad, void* stream);
+int cfd_int_pad_crop(const float* in, float* out, long n, int H, int W, int pad, void* stream);   // (n, H+pad, W+pad) -> (n, H, W)
+int cfd_int_pad_embed(const float* in, float* out, long n, int H, int W, int pad, void* stream);  // (n, H, W) -> (n, H+pad, W+pad), zero band
+
 // Wide-channel route (wide.hip): layers with more than 32 input or output channels, up to CFD_WIDE_MAX, fp32 storage.
 #define CFD_WIDE_MAX 128
 int cfd_int_wide_mix(const cfd_plan* p, const float* xh, const float* w1, const float* w2, float* z, int B, int Cin, int Cout,

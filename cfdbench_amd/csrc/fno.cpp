@@ -13,6 +13,8 @@ struct Layout {
     size_t n_act;    // floats of one (B,C,H,W) activation
     size_t n_modes;  // floats of one (B,C,2*m1,m2) complex tensor
     size_t off_acts, off_xh, off_z, off_gA, off_gB, off_gh, off_scratch, off_tmp;
+    size_t off_crop, off_coord;  // pad > 0 only: a_L cropped to the data grid (B,C,H,W) fp32; the data grid's coordinate tables
+    size_t n_crop;               // floats of one (B,C,H,W) activation on the data grid
     size_t head_off;  // byte offset of the training head's partial records inside the scratch region (0 in inference)
     size_t scratch_bytes, total_bytes;
     int n_acts, n_xh;
@@ -26,12 +28,28 @@ size_t stemg_offset(const cfd_plan* p, int B, int C, int HW) {
     return cfd_align_up(cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256) + cfd_chan_wgrad_workspace_bytes(B, C, C, HW), 256);
 }
 
+// The host-side view of `p` the lifting layer's gradient takes on a padded shape: the DATA grid's extents and coordinate tables (`coords`:
+// the table k_stem_pad left in the workspace).  Only H, W, d_gx and d_gy of a plan are read on that path.  pad == 0: the plan itself.
+cfd_plan data_plan(const cfd_plan* p, const cfd_fno_shape* s, float* coords) {
+    cfd_plan dp = *p;
+    if (s->pad > 0) {
+        dp.H = s->H;
+        dp.W = s->W;
+        dp.d_gx = coords;
+        dp.d_gy = coords ? coords + CFD_PAD_COORD_GY : nullptr;
+    }
+    return dp;
+}
+
 Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int dt = CFD_DT_F32) {
     Layout L{};
     const size_t esz = cfd_dt_size(dt);  // bytes of one stored activation
-    const size_t HW = (size_t)s->H * s->W;
+    // domain padding (shape.pad > 0): activations, input gradients and everything a block phase sizes live on the padded grid HWp (the
+    // plan's); the head, the loss and the lifting layer's gradient on the data grid HW.  pad == 0: HWp == HW, the layout of every earlier ABI.
+    const size_t HW = (size_t)s->H * s->W, HWp = (size_t)(s->H + s->pad) * (s->W + s->pad);
     const int C = s->hidden, B = s->B;
-    L.n_act = (size_t)B * C * HW;
+    L.n_act = (size_t)B * C * HWp;
+    L.n_crop = (size_t)B * C * HW;
     L.n_modes = (size_t)B * C * 2 * s->modes1 * s->modes2 * 2;
     L.n_acts = training ? s->num_layers + 1 : 2;
     L.n_xh = training ? s->num_layers : 1;
@@ -49,17 +67,22 @@ Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int 
         // both weight-gradient partial buffers of a block are alive until the block's input-gradient kernel has reduced
         // them (cfd_tail.h): spectral partials first, the 1x1-conv partials behind them
         scratch = max2(scratch, cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256) +
-                                    cfd_chan_wgrad_workspace_bytes(B, C, C, (int)HW));
-        scratch = max2(scratch, cfd_fno_stem_bwd_workspace_bytes(p, B, s->in_chan, s->n_case_params, C));
+                                    cfd_chan_wgrad_workspace_bytes(B, C, C, (int)HWp));
+        const cfd_plan dp = data_plan(p, s, nullptr);
+        scratch = max2(scratch, cfd_fno_stem_bwd_workspace_bytes(&dp, B, s->in_chan, s->n_case_params, C));
         // the lifting layer's sums of k_block<.., STEMG> live behind the two weight-gradient partial regions of the last block phase
-        scratch = max2(scratch, stemg_offset(p, B, C, (int)HW) + cfd_int_stemg_part_bytes(p, B, C));
+        scratch = max2(scratch, stemg_offset(p, B, C, (int)HWp) + cfd_int_stemg_part_bytes(p, B, C));
         // round 6: the training head's partial records behind everything a block phase writes -- with CFD_TRAIN_DEFER_HEAD they are read
         // by backward phase 1's block kernel, AFTER that phase's weight-gradient producers have written their partials into the regions above
-        L.head_off = cfd_align_up(stemg_offset(p, B, C, (int)HW) + cfd_int_stemg_part_bytes(p, B, C), 256);
+        L.head_off = cfd_align_up(stemg_offset(p, B, C, (int)HWp) + cfd_int_stemg_part_bytes(p, B, C), 256);
         scratch = max2(scratch, L.head_off + cfd_fno_head_workspace_bytes(B, C, s->head, s->out_chan, (int)HW));
     }
     L.scratch_bytes = scratch;
     L.off_scratch = take(scratch);
+    if (s->pad > 0) {
+        L.off_crop = take(L.n_crop * sizeof(float));
+        L.off_coord = take(CFD_PAD_COORD_FLOATS * sizeof(float));
+    }
     L.total_bytes = off;
     return L;
 }
@@ -67,9 +90,14 @@ Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int 
 // hidden 33 .. CFD_WIDE_MAX: the wide-channel route (wide.hip), fp32 activation storage only; the same for many-modes plans (dft_many.hip)
 int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int dt = CFD_DT_F32) {
     CFD_REQUIRE(p && s, CFD_ERR_INVALID_ARG, "%s: NULL plan/shape", fn);
-    CFD_REQUIRE(p->H == s->H && p->W == s->W && p->m1 == s->modes1 && p->m2 == s->modes2, CFD_ERR_INVALID_ARG,
-                "%s: plan is for %dx%d modes (%d,%d) but shape says %dx%d modes (%d,%d)", fn, p->H, p->W, p->m1, p->m2,
-                s->H, s->W, s->modes1, s->modes2);
+    CFD_REQUIRE(s->pad >= 0, CFD_ERR_INVALID_ARG, "%s: pad=%d (0 = no domain padding)", fn, s->pad);
+    CFD_REQUIRE(s->pad == 0 || (s->H >= 2 && s->W >= 2), CFD_ERR_INVALID_ARG, "%s: pad=%d needs a data grid of at least 2x2 (got %dx%d)", fn,
+                s->pad, s->H, s->W);
+    // the plan is the grid the FnoBlocks run on: the data grid plus `pad` rows at the bottom and `pad` columns at the right
+    CFD_REQUIRE(p->H == s->H + s->pad && p->W == s->W + s->pad && p->m1 == s->modes1 && p->m2 == s->modes2, CFD_ERR_INVALID_ARG,
+                "%s: plan is for %dx%d modes (%d,%d) but shape says data grid %dx%d + pad %d = %dx%d modes (%d,%d)", fn, p->H, p->W, p->m1,
+                p->m2, s->H, s->W, s->pad, s->H + s->pad, s->W + s->pad, s->modes1, s->modes2);
+    CFD_REQUIRE(s->pad == 0 || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "%s: pad=%d: bf16 activation storage needs pad = 0", fn, s->pad);
     CFD_REQUIRE(s->B >= 1, CFD_ERR_INVALID_ARG, "%s: empty batch", fn);
     CFD_REQUIRE(s->num_layers >= 0 && s->num_layers <= CFD_MAX_LAYERS, CFD_ERR_UNSUPPORTED, "%s: num_layers=%d (max %d)", fn,
                 s->num_layers, CFD_MAX_LAYERS);
@@ -86,8 +114,8 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     // elements (at 128 x 128 and head width 128: B <= 1023): refuse what would wrap
     if (p->W > 80) {
         const long long widest = s->hidden > s->head ? s->hidden : s->head;
-        CFD_REQUIRE((long long)s->B * widest * s->H * s->W <= 0x7fffffffLL, CFD_ERR_UNSUPPORTED,
-                    "%s: B=%d at %dx%d, width %d: more than 2^31 - 1 activation elements per tensor", fn, s->B, s->H, s->W, (int)widest);
+        CFD_REQUIRE((long long)s->B * widest * p->H * p->W <= 0x7fffffffLL, CFD_ERR_UNSUPPORTED,
+                    "%s: B=%d at %dx%d, width %d: more than 2^31 - 1 activation elements per tensor", fn, s->B, p->H, p->W, (int)widest);
     }
     return CFD_OK;
 }
@@ -102,7 +130,8 @@ Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, ch
     Deferred d{};
     // the wide route (hidden > 32), the many-modes route and the head's channel route (out_chan > 2) have none of the fused kernels
     // that carry a deferred job: every flag is ignored there
-    if (C > 32 || p->many || s->out_chan > 2) return d;
+    // -- and so does a padded shape (pad > 0), whatever plan it lands on: its lifting layer and head are kernels of their own (pad.hip)
+    if (C > 32 || p->many || s->out_chan > 2 || s->pad > 0) return d;
     d.scale = (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     const float* gA = (const float*)(base + L.off_gA);
     const float* gB = (const float*)(base + L.off_gB);
@@ -118,12 +147,12 @@ Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, ch
 }  // namespace
 
 extern "C" size_t cfd_fno_workspace_bytes(const cfd_plan* p, const cfd_fno_shape* s, int training) {
-    if (!p || !s || s->B < 1) return 0;
+    if (!p || !s || s->B < 1 || s->pad < 0) return 0;
     return make_layout(p, s, training).total_bytes;
 }
 
 extern "C" size_t cfd_fno_workspace_bytes_ex(const cfd_plan* p, const cfd_fno_shape* s, int training, int act_dtype) {
-    if (!p || !s || s->B < 1 || (act_dtype != CFD_DT_F32 && act_dtype != CFD_DT_BF16)) return 0;
+    if (!p || !s || s->B < 1 || s->pad < 0 || (act_dtype != CFD_DT_F32 && act_dtype != CFD_DT_BF16)) return 0;
     return make_layout(p, s, training, act_dtype).total_bytes;
 }
 
@@ -147,7 +176,7 @@ extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, con
     const int dt = act_dtype;
     const Layout L = make_layout(p, s, training, dt);
     char* base = (char*)ws;
-    const int B = s->B, C = s->hidden, HW = s->H * s->W, NL = s->num_layers;
+    const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
     const size_t esz = cfd_dt_size(dt);
     auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)(training ? l : (l & 1)) * L.n_act * esz); };
     auto xh_buf = [&](int l) { return (float*)(base + L.off_xh) + (size_t)(training ? l : 0) * L.n_modes; };
@@ -155,8 +184,12 @@ extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, con
     void* scratch = base + L.off_scratch;
 
     // round 6: on 64 x 64 the lifting layer rides in the first forward transform (one launch, one activation-sized read less)
-    const bool sd = dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
-    if (!sd)
+    // (not with domain padding: the fused kernel writes the unpadded layout with the plan's coordinates)
+    const bool sd = pad == 0 && dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
+    if (pad > 0)  // the lifting layer on the data grid, written into the padded layout with its zero band (pad.hip)
+        CFD_TRY(cfd_int_stem_pad(inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), (float*)(base + L.off_coord), B,
+                                 s->in_chan, s->n_case_params, C, s->H, s->W, pad, stream));
+    else if (!sd)
         CFD_TRY(cfd_int_fno_stem_fwd(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, act_buf(0), B, s->in_chan,
                                      s->n_case_params, C, dt, stream));
     for (int l = 0; l < NL; ++l) {  // FnoBlock.forward, fno2d.py:106-112
@@ -171,11 +204,16 @@ extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, con
             CFD_TRY(cfd_fno_block_fwd(p, (const float*)act_buf(l), z, prm->w0_w[l], prm->w0_b[l], (float*)act_buf(l + 1), B, C, C, act, stream));
         } else {  // bf16 storage: 1x1 conv into an fp32 scratch tensor, inverse transform added to it, ONE rounding on the store
             float* tmp = (float*)(base + L.off_tmp);
-            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HW, act, 0, dt, stream));
+            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HWp, act, 0, dt, stream));
             CFD_TRY(cfd_int_spectral_idft(p, z, tmp, nullptr, act_buf(l + 1), B * C, 1, dt, stream));
         }
     }
-    CFD_TRY(cfd_int_fno_head_fwd(act_buf(NL), mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
+    const void* aL = act_buf(NL);
+    if (pad > 0) {  // x[..., :-pad, :-pad] in front of fc1 (fno2d.py:225-226): the head kernels index flat H W
+        CFD_TRY(cfd_int_pad_crop((const float*)aL, (float*)(base + L.off_crop), (long)B * C, s->H, s->W, pad, stream));
+        aL = base + L.off_crop;
+    }
+    CFD_TRY(cfd_int_fno_head_fwd(aL, mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
                                  scratch, B, C, s->head, s->out_chan, HW, NL > 0, dt, stream));
     return CFD_OK;
 }
@@ -216,7 +254,7 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
     const int dt = act_dtype;
     const Layout L = make_layout(p, s, 1, dt);
     char* base = (char*)ws;
-    const int B = s->B, C = s->hidden, HW = s->H * s->W, NL = s->num_layers;
+    const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
     const size_t esz = cfd_dt_size(dt);
     auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)l * L.n_act * esz); };
     auto xh_buf = [&](int l) { return (float*)(base + L.off_xh) + (size_t)l * L.n_modes; };
@@ -229,8 +267,11 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
     const Deferred df = deferred(p, s, L, base, which, dt, flags, inputs, mask);
     hipStream_t side = cfd_side_fork((hipStream_t)stream, df.scale ? 0 : 1);
     if (!df.scale) CFD_TRY(cfd_label_energy_coef(label, mask, sums, coef, scratch, B, s->out_chan, HW, which, upstream, side));
-    const bool sd = dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
-    if (!sd)
+    const bool sd = pad == 0 && dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
+    if (pad > 0)
+        CFD_TRY(cfd_int_stem_pad(inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), (float*)(base + L.off_coord), B,
+                                 s->in_chan, s->n_case_params, C, s->H, s->W, pad, stream));
+    else if (!sd)
         CFD_TRY(cfd_int_fno_stem_fwd(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, act_buf(0), B, s->in_chan, s->n_case_params, C,
                                      dt, stream));
     for (int l = 0; l < NL; ++l) {  // FnoBlock.forward, fno2d.py:106-112
@@ -245,23 +286,35 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
             CFD_TRY(cfd_fno_block_fwd(p, (const float*)act_buf(l), z, prm->w0_w[l], prm->w0_b[l], (float*)act_buf(l + 1), B, C, C, act, stream));
         } else {
             float* tmp = (float*)(base + L.off_tmp);
-            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HW, act, 0, dt, stream));
+            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HWp, act, 0, dt, stream));
             CFD_TRY(cfd_int_spectral_idft(p, z, tmp, nullptr, act_buf(l + 1), B * C, 1, dt, stream));
         }
     }
     CFD_TRY(cfd_side_join((hipStream_t)stream, side));
+    // Domain padding: the head runs on the data grid -- a_L cropped into the compact region, d loss / d a_L written compactly into gB
+    // (free until backward phase 1 writes it) and embedded into gA with a zero band: what autograd's slice backward produces.
+    const void* aL = act_buf(NL);
+    float* ga = gA;
+    if (pad > 0) {
+        CFD_TRY(cfd_int_pad_crop((const float*)aL, (float*)(base + L.off_crop), (long)B * C, s->H, s->W, pad, stream));
+        aL = base + L.off_crop;
+        ga = (float*)(base + L.off_gB);
+    }
     // deferred normaliser: the mse coefficient by value, sum (label*mask)^2 and the count leave the head's reduction (sums[2], sums[3])
     if (C > 32) {  // wide route: head forward (sums[0..1]; sums[2..3] and coef came from cfd_label_energy_coef), then its backward
-        CFD_TRY(cfd_int_wide_head_fwd((const float*)act_buf(NL), mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
+        CFD_TRY(cfd_int_wide_head_fwd((const float*)aL, mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
                                       scratch, B, C, s->out_chan, HW, NL > 0, stream, 0));
-        return cfd_int_wide_head_bwd((const float*)act_buf(NL), mask, label, preds, nullptr, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, gA,
-                                     g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->out_chan, HW, NL > 0, stream);
+        CFD_TRY(cfd_int_wide_head_bwd((const float*)aL, mask, label, preds, nullptr, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, ga,
+                                      g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->out_chan, HW, NL > 0, stream));
+    } else {
+        const float count = (float)((double)B * s->out_chan * HW);
+        HeadTail ht{};
+        CFD_TRY(cfd_int_fno_head_train_f(aL, mask, label, df.scale ? nullptr : coef, upstream / count, 0.f, df.scale ? count : 0.f,
+                                         prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums, ga, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b,
+                                         (char*)scratch + L.head_off, B, C, s->head, s->out_chan, HW, NL > 0, dt, stream, df.head ? &ht : nullptr));
     }
-    const float count = (float)((double)B * s->out_chan * HW);
-    HeadTail ht{};
-    return cfd_int_fno_head_train_f(act_buf(NL), mask, label, df.scale ? nullptr : coef, upstream / count, 0.f, df.scale ? count : 0.f,
-                                    prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums, gA, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b,
-                                    (char*)scratch + L.head_off, B, C, s->head, s->out_chan, HW, NL > 0, dt, stream, df.head ? &ht : nullptr);
+    if (pad > 0) CFD_TRY(cfd_int_pad_embed(ga, gA, (long)B * C, s->H, s->W, pad, stream));
+    return CFD_OK;
 }
 
 // One phase of the backward pass: 0 = projection head (+ loss gradient), 1 .. L = FnoBlock L-phase (the blocks in reverse
@@ -297,7 +350,7 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     const int dt = act_dtype;
     const Layout L = make_layout(p, s, 1, dt);
     char* base = (char*)ws;
-    const int B = s->B, C = s->hidden, HW = s->H * s->W, NL = s->num_layers;
+    const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
     const size_t esz = cfd_dt_size(dt);
     CFD_REQUIRE(phase >= 0 && phase <= NL + 1, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: phase %d outside 0..%d", phase, NL + 1);
     auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)l * L.n_act * esz); };
@@ -309,6 +362,12 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     void* scratch = base + L.off_scratch;
     if (phase == 0) {
         CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_backward_phase: phase 0 with bf16 storage (the head ran in cfd_fno_forward_train_ex)");
+        if (pad > 0) {  // the head on the data grid: a_L as the forward call cropped it, the gradient compact in gB, embedded into gA
+            CFD_TRY(cfd_fno_head_bwd((const float*)(base + L.off_crop), mask, label, preds, gpreds_ext, coef, prm->fc1_w, prm->fc1_b,
+                                     prm->fc2_w, gB, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->head, s->out_chan, HW, NL > 0,
+                                     stream));
+            return cfd_int_pad_embed(gB, gA, (long)B * C, s->H, s->W, pad, stream);
+        }
         return cfd_fno_head_bwd((const float*)act_buf(NL), mask, label, preds, gpreds_ext, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, gA,
                                 g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->head, s->out_chan, HW, NL > 0,
                                 stream);
@@ -319,15 +378,22 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     // Round 5: where the fused FnoBlock kernel runs the last block phase (l = 0), it emits the six per-(entry, channel) sums the lifting
     // layer's gradient needs instead of storing g_0 for a pass that reads it back (cfd_tail.h: CfdStemG): one activation-sized write and
     // the k_chan_wgrad_stem launch less.  Both phases evaluate the same predicate.
-    const bool stemg = dt == CFD_DT_F32 && NL >= 1 &&
+    // (Not with domain padding: g_0 lives on the padded grid and the sums would be taken with the plan's coordinates.)
+    const bool stemg = pad == 0 && dt == CFD_DT_F32 && NL >= 1 &&
                        cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, z);
-    float* stem_part = (float*)((char*)scratch + stemg_offset(p, B, C, HW));
+    float* stem_part = (float*)((char*)scratch + stemg_offset(p, B, C, HWp));
     const Deferred df = deferred(p, s, L, base, which, dt, flags, inputs, mask);
     CFD_REQUIRE(!df.head || sums, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: CFD_TRAIN_DEFER_HEAD needs the `sums` of the forward call");
     if (phase == NL + 1) {
         if (stemg && df.stem) return CFD_OK;  // cfd_fno_adam_step's launch finishes the lifting layer's gradient
         if (stemg)
             return cfd_int_stemg_combine(p, stem_part, case_params, g->fc0_w, g->fc0_b, B, C, s->in_chan, s->n_case_params, stream);
+        if (pad > 0) {  // g_0 cropped into the free gradient buffer; the lifting layer's gradient on the data grid with ITS coordinates
+            CFD_TRY(cfd_int_pad_crop(gcur, gnext, (long)B * C, s->H, s->W, pad, stream));
+            const cfd_plan dp = data_plan(p, s, (float*)(base + L.off_coord));
+            return cfd_fno_stem_bwd(&dp, gnext, inputs, mask, case_params, g->fc0_w, g->fc0_b, scratch, B, s->in_chan, s->n_case_params, C,
+                                    stream);
+        }
         return cfd_fno_stem_bwd(p, gcur, inputs, mask, case_params, g->fc0_w, g->fc0_b, scratch, B, s->in_chan,
                                 s->n_case_params, C, stream);
     }
@@ -342,8 +408,8 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
         CFD_TRY(cfd_spectral_dft(p, gcur, gh, B * C, 0, stream));
         CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, xh_buf(l), gh, prm->spec_w1[l], prm->spec_w2[l], z, g->spec_w1[l],
                                                g->spec_w2[l], scratch, B, C, C, stream, nullptr));
-        CFD_TRY(cfd_int_chan_wgrad_dt(gcur, act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HW, act, dt, stream, nullptr));
-        CFD_TRY(cfd_chanmix(gcur, prm->w0_w[l], nullptr, tmp, B, C, C, HW, 0, 1, stream));
+        CFD_TRY(cfd_int_chan_wgrad_dt(gcur, act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HWp, act, dt, stream, nullptr));
+        CFD_TRY(cfd_chanmix(gcur, prm->w0_w[l], nullptr, tmp, B, C, C, HWp, 0, 1, stream));
         return cfd_int_spectral_idft_grad(p, z, tmp, act ? act_buf(l) : nullptr, gnext, B * C, dt, stream);
     }
     // the reductions of both weight gradients ride in front of the input-gradient kernel's launch (cfd_tail.h); whatever
@@ -353,7 +419,7 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     // takes 53 us instead of 26 -- it needs the wave slots the streaming kernel occupies -- and the phase is no shorter.
     hipStream_t side = cfd_side_fork((hipStream_t)stream, 2);
     CfdReduceTail tail{};
-    CFD_TRY(cfd_int_chan_wgrad(gcur, (const float*)act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HW, act, side, &tail.chan));
+    CFD_TRY(cfd_int_chan_wgrad(gcur, (const float*)act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HWp, act, side, &tail.chan));
     CFD_TRY(cfd_spectral_dft(p, gcur, gh, B * C, 0, stream));
     CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, xh_buf(l), gh, prm->spec_w1[l], prm->spec_w2[l], z, g->spec_w1[l],
                                            g->spec_w2[l], scratch, B, C, C, stream, &tail.spec));

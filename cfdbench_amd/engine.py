@@ -314,10 +314,11 @@ class FnoTrainEngine:
         if key == self._shape_key:
             return
         c = self.cfg
-        self._route_defers = self._model_defers and W <= 80  # (cfd_plan_create: every plan with W > 80 is a many-modes plan)
-        self.plan = _lib.plan(H, W, c["modes1"], c["modes2"], self.device.index)
+        pad = int(c.get("padding", 0))  # Fno2d(padding=): the plan is the padded grid's; a padded shape defers nothing (fno.cpp: deferred())
+        self._route_defers = self._model_defers and W + pad <= 80 and pad == 0  # (cfd_plan_create: every plan with W > 80 is a many-modes plan)
+        self.plan = _lib.plan(H + pad, W + pad, c["modes1"], c["modes2"], self.device.index)
         self.shape = FnoShape(B, H, W, in_chan, c["out_chan"], case_params.shape[1], c["hidden"], self.L, c["modes1"],
-                              c["modes2"], c["head"])
+                              c["modes2"], c["head"], pad)
         nbytes = self.api.size("cfd_fno_workspace_bytes_ex", self.plan, ctypes.byref(self.shape), 1, self.act_dtype)
         if nbytes == 0:
             raise RuntimeError("cfd_fno_workspace_bytes_ex returned 0 for this shape / activation type")

@@ -329,8 +329,9 @@ class FnoForwardFn(torch.autograd.Function):
             raise RuntimeError(f"FnoForwardFn: expected {6 + 4 * L} parameter tensors, got {len(params)}")
         if params[0].shape[1] != in_chan + 3 + P:
             raise RuntimeError(f"Fno2d: fc0 expects {params[0].shape[1]} features but inputs provide {in_chan}+3+{P}")
-        plan = _lib.plan(H, W, m1, m2, inputs.device.index)
-        shape = FnoShape(B, H, W, in_chan, out_chan, P, C, L, m1, m2, head)
+        pad = int(cfg.get("padding", 0))  # Fno2d(padding=): the blocks run on (H + pad, W + pad), which is the grid the plan is for
+        plan = _lib.plan(H + pad, W + pad, m1, m2, inputs.device.index)
+        shape = FnoShape(B, H, W, in_chan, out_chan, P, C, L, m1, m2, head, pad)
         flat = [(_creal(p.detach()) if p.is_complex() else _f32c(p.detach())) for p in params]
         pstruct = _param_struct([t.data_ptr() for t in flat], L)
         # needs_input_grad reflects requires_grad whatever the grad mode is (and grad mode is always off inside

@@ -10,6 +10,7 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``lr_scheduler`` (step = the reference's StepLR | plateau = ReduceLROnPlateau(lr_scheduler_factor, lr_scheduler_patience) |
     cosine), ``early_stop`` (1: stop after early_stopping_patience evaluations without early_stopping_delta improvement),
     ``gradient_accumulation_steps`` (args.py:323; micro-batches per optimiser step),
+    ``fno_padding`` (Fno2d's ``padding``: the FnoBlocks run on a grid zero-padded by that many rows and columns; default None),
     ``graph`` (1: the autograd train step -- forward, loss, backward, Adam -- is captured once as a HIP graph and replayed per batch;
     single process, no gradient accumulation, models without per-step host state, i.e. not the ResNet's dropout),
     ``dtype`` ("bf16": the FNO's activations between kernels are stored as bf16 -- test_multistep: BASELINE configs[4];
@@ -44,7 +45,10 @@ _FLAGS: Dict[str, Any] = dict(
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1,
+    # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
+    fno_padding=None,
 )
+_OPTIONAL_INT = ("fno_padding",)  # flags whose default is None: parsed as int when given
 
 
 class Args:
@@ -62,7 +66,7 @@ class Args:
         ap = argparse.ArgumentParser(allow_abbrev=False)
         for k, v in _FLAGS.items():
             names = [f"--{k}"] + (["--data"] if k == "data_name" else [])
-            ap.add_argument(*names, dest=k, type=type(v), default=getattr(self, k))
+            ap.add_argument(*names, dest=k, type=int if k in _OPTIONAL_INT else type(v), default=getattr(self, k))
         ns = ap.parse_args(argv)
         for k in _FLAGS:
             setattr(self, k, getattr(ns, k))
@@ -97,3 +101,7 @@ def is_args_valid(args: Args) -> None:
         assert not args.fused, "--graph 1 captures the autograd step; the fused FNO engine has its own launch path"
         assert args.gradient_accumulation_steps == 1, "--graph 1 captures one optimiser step per batch"
     assert args.unet_insert_case_params_at in ("input", "hidden")
+    if args.fno_padding is not None:
+        assert args.model == "fno", "--fno_padding is Fno2d's domain padding"
+        assert args.fno_padding >= 1, "--fno_padding must be >= 1 (leave it out for no padding)"
+        assert args.dtype == "fp32", "--fno_padding runs with fp32 activation storage (--dtype bf16 is refused by the library)"

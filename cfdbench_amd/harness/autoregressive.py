@@ -36,7 +36,7 @@ def init_model(args) -> AutoCfdModel:
     if args.model == "fno":
         return Fno2d(in_chan=args.in_chan, out_chan=args.out_chan, n_case_params=n_case_params, loss_fn=loss_fn,
                      num_layers=args.fno_depth, hidden_dim=args.fno_hidden_dim, modes1=args.fno_modes_x,
-                     modes2=args.fno_modes_y)
+                     modes2=args.fno_modes_y, padding=getattr(args, "fno_padding", None))
     if args.model == "auto_deeponet":  # autoregressive.py:58-69
         return AutoDeepONet(branch_dim=n_cols * n_rows + n_case_params, trunk_dim=2, loss_fn=loss_fn,
                             width=args.deeponet_width, trunk_depth=args.trunk_depth, branch_depth=args.branch_depth,

@@ -59,7 +59,7 @@ extern "C" {
  * changes (500, round 5: the statistics records of cfd_conv2d_fwd_stats / cfd_batchnorm_fwd_stats are (C, slots, 4) floats since
  * round 4 -- a caller that still allocates (C, slots, 2) must fail at load time, not write out of bounds; the default of the
  * "act_pieces" knob is 3).  The Python binding refuses a library whose version differs (cfdbench_amd/_capi.py). */
-#define CFD_ABI_VERSION 601
+#define CFD_ABI_VERSION 602
 int cfd_version(void);
 const char* cfd_last_error(void);
 
@@ -475,10 +475,20 @@ int cfd_dropout_gelu_bwd_step(const float* x, const float* gy, float* gx, size_t
                               const unsigned long long* step, void* stream);
 
 /* ---- whole Auto-FNO (Fno2d.forward, fno2d.py:178-242; loss.backward() at train_auto.py:255) ---------------*/
+/* H, W are the DATA grid: the extents of inputs, mask, label and preds.  pad (the reference's Fno2d(padding=pad), fno2d.py:219-226; 0 = none)
+ * zero-pads the lifting layer's output by `pad` rows at the bottom and `pad` columns at the right, runs every FnoBlock on the
+ * (H + pad) x (W + pad) grid and crops back to H x W in front of fc1.  The plan handed over with such a shape is the PADDED grid's,
+ * cfd_plan_create(H + pad, W + pad, modes1, modes2) -- the mode limits are the padded grid's -- so H + pad, W + pad <= 128; the data
+ * grid's coordinate features are np.linspace(0, 1, H) / (0, 1, W) all the same.  pad < 0, pad > 0 with H < 2 or W < 2, or a plan of
+ * another grid: CFD_ERR_INVALID_ARG; pad > 0 with bf16 activation storage: CFD_ERR_UNSUPPORTED.  With pad > 0 the CFD_TRAIN_DEFER_*
+ * flags are ignored (gradients are final after the pass) and the step makes three more activation-sized passes (pad.hip: a_L cropped in
+ * front of the head, the head's gradient embedded, g_0 cropped in front of the lifting layer's gradient).  Appended in ABI 602: a
+ * caller that fills the first eleven fields of a zeroed struct means pad = 0. */
 typedef struct {
     int B, H, W;
     int in_chan, out_chan, n_case_params;
     int hidden, num_layers, modes1, modes2, head;
+    int pad;
 } cfd_fno_shape;
 
 typedef struct { /* device pointers, reference state_dict order (SURVEY.md 8b "Checkpoint ABI") */
