@@ -9,9 +9,9 @@ import ctypes
 import os
 import threading
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Tuple
 
-from ._capi import CApi, CfdError
+from ._capi import CApi, CfdError, FnoShape
 
 # CFDBENCH_AMD_LIB: explicit path of another build of the same library (kernel experiments: tools/build_variant.sh); there is
 # still no fallback -- a path that does not exist fails exactly like a missing default build
@@ -68,3 +68,25 @@ def plan(H: int, W: int, m1: int, m2: int, device_index: int) -> int:
                     p = api().plan_create(H, W, m1, m2)
                 _plans[key] = p
     return p
+
+
+class FnoCall(NamedTuple):
+    plan: int
+    shape: FnoShape
+    defers: bool  # the route honours CFD_TRAIN_DEFER_*
+
+
+def fno_call(cfg: dict, B: int, in_chan: int, H: int, W: int, n_case_params: int, device) -> FnoCall:
+    """What a whole-model C call needs besides its tensors, from ``Fno2d.abi_config()`` and one batch's extents: the plan and the
+    ``FnoShape``.  The one place that knows the domain-padding rule: ``Fno2d(padding=)`` runs its FnoBlocks on (H + pad, W + pad), so
+    that is the grid the plan is for, while the shape carries the data grid and ``pad``.
+
+    ``defers`` mirrors ``route()`` of csrc/fno.cpp (the table above it): the wide route (hidden > 32), the many-modes route (modes1 > 15
+    or modes2 > 16, or a plan wider than 80 columns: cfd_plan_create), the head's channel route (out_chan > 2) and a padded shape have
+    none of the kernels that carry a deferred job and ignore the flags, so their gradients are final after the pass.  Only
+    ``FnoTrainEngine.gradients()`` reads it."""
+    pad = int(cfg.get("padding", 0))
+    m1, m2 = cfg["modes1"], cfg["modes2"]
+    shape = FnoShape(B, H, W, in_chan, cfg["out_chan"], n_case_params, cfg["hidden"], cfg["num_layers"], m1, m2, cfg["head"], pad)
+    defers = cfg["hidden"] <= 32 and m1 <= 15 and m2 <= 16 and W + pad <= 80 and cfg["out_chan"] <= 2 and pad == 0
+    return FnoCall(plan(H + pad, W + pad, m1, m2, device.index), shape, defers)

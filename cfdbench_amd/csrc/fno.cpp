@@ -15,18 +15,14 @@ struct Layout {
     size_t off_acts, off_xh, off_z, off_gA, off_gB, off_gh, off_scratch, off_tmp;
     size_t off_crop, off_coord;  // pad > 0 only: a_L cropped to the data grid (B,C,H,W) fp32; the data grid's coordinate tables
     size_t n_crop;               // floats of one (B,C,H,W) activation on the data grid
-    size_t head_off;  // byte offset of the training head's partial records inside the scratch region (0 in inference)
+    // byte offsets inside the scratch region (training only): the 1x1 weight-gradient partials, the lifting layer's sum records, the
+    // training head's partial records
+    size_t off_chan_part, off_stemg, head_off;
     size_t scratch_bytes, total_bytes;
     int n_acts, n_xh;
 };
 
 size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-
-// byte offset of the lifting layer's sum records inside the scratch region (behind the spectral and the 1x1 weight-gradient partials,
-// which the tail workgroups of the same launch are still reading)
-size_t stemg_offset(const cfd_plan* p, int B, int C, int HW) {
-    return cfd_align_up(cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256) + cfd_chan_wgrad_workspace_bytes(B, C, C, HW), 256);
-}
 
 // The host-side view of `p` the lifting layer's gradient takes on a padded shape: the DATA grid's extents and coordinate tables (`coords`:
 // the table k_stem_pad left in the workspace).  Only H, W, d_gx and d_gy of a plan are read on that path.  pad == 0: the plan itself.
@@ -66,15 +62,18 @@ Layout make_layout(const cfd_plan* p, const cfd_fno_shape* s, int training, int 
         L.off_gh = take(L.n_modes * sizeof(float));
         // both weight-gradient partial buffers of a block are alive until the block's input-gradient kernel has reduced
         // them (cfd_tail.h): spectral partials first, the 1x1-conv partials behind them
-        scratch = max2(scratch, cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256) +
-                                    cfd_chan_wgrad_workspace_bytes(B, C, C, (int)HWp));
+        L.off_chan_part = cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256);
+        const size_t block_part = L.off_chan_part + cfd_chan_wgrad_workspace_bytes(B, C, C, (int)HWp);
+        scratch = max2(scratch, block_part);
         const cfd_plan dp = data_plan(p, s, nullptr);
         scratch = max2(scratch, cfd_fno_stem_bwd_workspace_bytes(&dp, B, s->in_chan, s->n_case_params, C));
-        // the lifting layer's sums of k_block<.., STEMG> live behind the two weight-gradient partial regions of the last block phase
-        scratch = max2(scratch, stemg_offset(p, B, C, (int)HWp) + cfd_int_stemg_part_bytes(p, B, C));
+        // the lifting layer's sums of k_block<.., STEMG> live behind the two weight-gradient partial regions of the last block phase (which
+        // the tail workgroups of the same launch are still reading)
+        L.off_stemg = cfd_align_up(block_part, 256);
+        scratch = max2(scratch, L.off_stemg + cfd_int_stemg_part_bytes(p, B, C));
         // round 6: the training head's partial records behind everything a block phase writes -- with CFD_TRAIN_DEFER_HEAD they are read
         // by backward phase 1's block kernel, AFTER that phase's weight-gradient producers have written their partials into the regions above
-        L.head_off = cfd_align_up(stemg_offset(p, B, C, (int)HWp) + cfd_int_stemg_part_bytes(p, B, C), 256);
+        L.head_off = cfd_align_up(L.off_stemg + cfd_int_stemg_part_bytes(p, B, C), 256);
         scratch = max2(scratch, L.head_off + cfd_fno_head_workspace_bytes(B, C, s->head, s->out_chan, (int)HW));
     }
     L.scratch_bytes = scratch;
@@ -120,35 +119,111 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     return CFD_OK;
 }
 
-// Which deferrals of `flags` apply to this shape (the forward call, every backward phase and cfd_fno_adam_step evaluate the same thing).
-struct Deferred {
+// The workspace as one call sees it: the Layout and a view of every region.  Every entry builds one and does no offset arithmetic of its own.
+struct View {
+    Layout L;
+    char* base;
+    size_t act_stride;  // bytes of one stored activation
+    bool training;
+    View(const cfd_plan* p, const cfd_fno_shape* s, int training_, int dt, void* ws)
+        : L(make_layout(p, s, training_, dt)), base((char*)ws), act_stride(L.n_act * cfd_dt_size(dt)), training(training_ != 0) {}
+    // a_l: training keeps a_0 .. a_L for the backward pass, inference ping-pongs between two buffers
+    void* act(int l) const { return base + L.off_acts + (size_t)(training ? l : (l & 1)) * act_stride; }
+    float* xh(int l) const { return (float*)(base + L.off_xh) + (size_t)(training ? l : 0) * L.n_modes; }
+    float* z() const { return (float*)(base + L.off_z); }
+    float* tmp() const { return (float*)(base + L.off_tmp); }  // bf16 storage only
+    float* gA() const { return (float*)(base + L.off_gA); }
+    float* gB() const { return (float*)(base + L.off_gB); }
+    float* gh() const { return (float*)(base + L.off_gh); }
+    char* scratch() const { return base + L.off_scratch; }  // spectral weight-gradient partials (and whatever else is alone)
+    char* scratch2() const { return scratch() + L.off_chan_part; }  // the 1x1 weight-gradient partials behind them
+    float* stem_part() const { return (float*)(scratch() + L.off_stemg); }  // the lifting layer's sum records
+    char* head_rec() const { return scratch() + L.head_off; }  // the training head's partial records
+    float* crop() const { return (float*)(base + L.off_crop); }  // pad > 0 only
+    float* coord() const { return (float*)(base + L.off_coord); }  // pad > 0 only
+};
+
+// THE route rule: which fusions and deferrals a call may use.  Evaluated once per entry; the forward call, every backward phase and
+// cfd_fno_adam_step evaluate the same thing and so agree.  A shape is narrow unless one of the exclusions in the first column holds.
+//
+//                              stem_in_dft              stemg                    scale            head                       stem
+//   hidden > 32                no (dft_stem_ok)         no (stemg_ok: C <= 24)   no               no                         no
+//   p->many                    no (dft_stem_ok)         no (stemg_ok)            no               no                         no
+//   out_chan > 2               as narrow                as narrow                no               no                         no
+//   pad > 0                    no                       no                       no               no                         no
+//   bf16 storage               no                       no                       as narrow        no                         no
+//   num_layers == 0            no                       no                       as narrow        no                         no
+//   narrow                     cfd_int_dft_stem_ok      cfd_int_stemg_ok         flag, which = 1  flag, block_bwd_fused      flag, stemg
+//
+// stem_in_dft: the lifting layer rides in the first forward transform (round 6: on 64 x 64 one launch and one activation-sized read less).
+//   Not with domain padding: the fused kernel writes the unpadded layout with the plan's coordinates.
+// stemg: round 5: where the fused FnoBlock kernel runs the last block phase (l = 0), it emits the six per-(entry, channel) sums the lifting
+//   layer's gradient needs instead of storing g_0 for a pass that reads it back (cfd_tail.h: CfdStemG): one activation-sized write and the
+//   k_chan_wgrad_stem launch less.  Not with domain padding: g_0 lives on the padded grid and the sums would be taken with the plan's coordinates.
+// scale / head / stem: the CFD_TRAIN_DEFER_* bits of `flags` that apply.  The wide route, the many-modes route and the head's channel route
+//   have none of the fused kernels that carry a deferred job, and a padded shape's lifting layer and head are kernels of their own (pad.hip):
+//   every flag is ignored there.  scale is the only one that bf16 storage keeps; stem implies stemg.
+struct Route {
+    bool stem_in_dft, stemg;
     bool scale, head, stem;
 };
-Deferred deferred(const cfd_plan* p, const cfd_fno_shape* s, const Layout& L, char* base, int which, int dt, int flags, const void* inputs,
-                  const void* mask) {
+Route route(const cfd_plan* p, const cfd_fno_shape* s, const View& v, int which, int dt, int flags, const void* inputs, const void* mask) {
     const int B = s->B, C = s->hidden, NL = s->num_layers;
-    Deferred d{};
-    // the wide route (hidden > 32), the many-modes route and the head's channel route (out_chan > 2) have none of the fused kernels
-    // that carry a deferred job: every flag is ignored there
-    // -- and so does a padded shape (pad > 0), whatever plan it lands on: its lifting layer and head are kernels of their own (pad.hip)
-    if (C > 32 || p->many || s->out_chan > 2 || s->pad > 0) return d;
-    d.scale = (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
-    const float* gA = (const float*)(base + L.off_gA);
-    const float* gB = (const float*)(base + L.off_gB);
-    const float* z = (const float*)(base + L.off_z);
+    const bool fusable = s->pad == 0 && dt == CFD_DT_F32 && NL >= 1;
+    const bool defers = !(C > 32 || p->many || s->out_chan > 2 || s->pad > 0);
+    Route r{};
+    r.stem_in_dft = fusable && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, v.act(0));
+    if (!v.training) return r;  // (inference has no gradient and defers nothing)
+    r.stemg = fusable && cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, v.z());
+    r.scale = defers && (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     // backward phase 1 = FnoBlock NL-1: gcur = gA, gnext = gB, aprev = a_{NL-1} when NL > 1
-    const void* aprev = NL > 1 ? (const void*)(base + L.off_acts + (size_t)(NL - 1) * L.n_act * cfd_dt_size(dt)) : nullptr;
-    d.head = (flags & CFD_TRAIN_DEFER_HEAD) && dt == CFD_DT_F32 && NL >= 1 && cfd_int_block_bwd_fused(p, B, C, gA, gB, aprev, z);
-    d.stem = (flags & CFD_TRAIN_DEFER_STEM) && dt == CFD_DT_F32 && NL >= 1 &&
-             cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, z);
-    return d;
+    r.head = defers && fusable && (flags & CFD_TRAIN_DEFER_HEAD) && cfd_int_block_bwd_fused(p, B, C, v.gA(), v.gB(), NL > 1 ? v.act(NL - 1) : nullptr, v.z());
+    r.stem = defers && (flags & CFD_TRAIN_DEFER_STEM) && r.stemg;
+    return r;
+}
+
+// The trunk: lifting layer and FnoBlocks, a_0 .. a_L into v.act() (Fno2d.forward up to fc1, fno2d.py:178-224)
+int trunk(const cfd_plan* p, const cfd_fno_shape* s, const cfd_fno_params* prm, const View& v, const Route& rt, int dt, const float* inputs,
+          const float* case_params, const float* mask, void* stream) {
+    const int B = s->B, C = s->hidden, HWp = p->H * p->W, NL = s->num_layers;
+    if (s->pad > 0)  // the lifting layer on the data grid, written into the padded layout with its zero band (pad.hip)
+        CFD_TRY(cfd_int_stem_pad(inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)v.act(0), v.coord(), B, s->in_chan,
+                                 s->n_case_params, C, s->H, s->W, s->pad, stream));
+    else if (!rt.stem_in_dft)
+        CFD_TRY(cfd_int_fno_stem_fwd(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, v.act(0), B, s->in_chan, s->n_case_params, C, dt,
+                                     stream));
+    for (int l = 0; l < NL; ++l) {  // FnoBlock.forward, fno2d.py:106-112
+        const int act = l > 0;
+        if (l == 0 && rt.stem_in_dft)
+            CFD_TRY(cfd_int_spectral_dft_stem(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)v.act(0), v.xh(0), B,
+                                              s->n_case_params, C, stream));
+        else
+            CFD_TRY(cfd_int_spectral_dft(p, v.act(l), v.xh(l), B * C, act, dt, stream));
+        CFD_TRY(cfd_spectral_mix(p, v.xh(l), prm->spec_w1[l], prm->spec_w2[l], v.z(), B, C, C, 0, stream));
+        if (dt == CFD_DT_F32) {
+            CFD_TRY(cfd_fno_block_fwd(p, (const float*)v.act(l), v.z(), prm->w0_w[l], prm->w0_b[l], (float*)v.act(l + 1), B, C, C, act, stream));
+        } else {  // bf16 storage: 1x1 conv into an fp32 scratch tensor, inverse transform added to it, ONE rounding on the store
+            CFD_TRY(cfd_int_chanmix(v.act(l), prm->w0_w[l], prm->w0_b[l], v.tmp(), B, C, C, HWp, act, 0, dt, stream));
+            CFD_TRY(cfd_int_spectral_idft(p, v.z(), v.tmp(), nullptr, v.act(l + 1), B * C, 1, dt, stream));
+        }
+    }
+    return CFD_OK;
+}
+
+// What the head reads: a_L, or with domain padding x[..., :-pad, :-pad] (fno2d.py:225-226) cropped into the compact region -- the head
+// kernels index flat H W
+int head_input(const cfd_fno_shape* s, const View& v, void* stream, const void** aL) {
+    *aL = v.act(s->num_layers);
+    if (s->pad == 0) return CFD_OK;
+    CFD_TRY(cfd_int_pad_crop((const float*)*aL, v.crop(), (long)s->B * s->hidden, s->H, s->W, s->pad, stream));
+    *aL = v.crop();
+    return CFD_OK;
 }
 
 }  // namespace
 
 extern "C" size_t cfd_fno_workspace_bytes(const cfd_plan* p, const cfd_fno_shape* s, int training) {
-    if (!p || !s || s->B < 1 || s->pad < 0) return 0;
-    return make_layout(p, s, training).total_bytes;
+    return cfd_fno_workspace_bytes_ex(p, s, training, CFD_DT_F32);
 }
 
 extern "C" size_t cfd_fno_workspace_bytes_ex(const cfd_plan* p, const cfd_fno_shape* s, int training, int act_dtype) {
@@ -174,47 +249,13 @@ extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, con
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_forward: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || !training, CFD_ERR_UNSUPPORTED, "cfd_fno_forward: bf16 activation storage is an inference path (training = 0)");
     const int dt = act_dtype;
-    const Layout L = make_layout(p, s, training, dt);
-    char* base = (char*)ws;
-    const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
-    const size_t esz = cfd_dt_size(dt);
-    auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)(training ? l : (l & 1)) * L.n_act * esz); };
-    auto xh_buf = [&](int l) { return (float*)(base + L.off_xh) + (size_t)(training ? l : 0) * L.n_modes; };
-    float* z = (float*)(base + L.off_z);
-    void* scratch = base + L.off_scratch;
-
-    // round 6: on 64 x 64 the lifting layer rides in the first forward transform (one launch, one activation-sized read less)
-    // (not with domain padding: the fused kernel writes the unpadded layout with the plan's coordinates)
-    const bool sd = pad == 0 && dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
-    if (pad > 0)  // the lifting layer on the data grid, written into the padded layout with its zero band (pad.hip)
-        CFD_TRY(cfd_int_stem_pad(inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), (float*)(base + L.off_coord), B,
-                                 s->in_chan, s->n_case_params, C, s->H, s->W, pad, stream));
-    else if (!sd)
-        CFD_TRY(cfd_int_fno_stem_fwd(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, act_buf(0), B, s->in_chan,
-                                     s->n_case_params, C, dt, stream));
-    for (int l = 0; l < NL; ++l) {  // FnoBlock.forward, fno2d.py:106-112
-        const int act = l > 0;
-        if (l == 0 && sd)
-            CFD_TRY(cfd_int_spectral_dft_stem(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), xh_buf(0), B,
-                                              s->n_case_params, C, stream));
-        else
-            CFD_TRY(cfd_int_spectral_dft(p, act_buf(l), xh_buf(l), B * C, act, dt, stream));
-        CFD_TRY(cfd_spectral_mix(p, xh_buf(l), prm->spec_w1[l], prm->spec_w2[l], z, B, C, C, 0, stream));
-        if (dt == CFD_DT_F32) {
-            CFD_TRY(cfd_fno_block_fwd(p, (const float*)act_buf(l), z, prm->w0_w[l], prm->w0_b[l], (float*)act_buf(l + 1), B, C, C, act, stream));
-        } else {  // bf16 storage: 1x1 conv into an fp32 scratch tensor, inverse transform added to it, ONE rounding on the store
-            float* tmp = (float*)(base + L.off_tmp);
-            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HWp, act, 0, dt, stream));
-            CFD_TRY(cfd_int_spectral_idft(p, z, tmp, nullptr, act_buf(l + 1), B * C, 1, dt, stream));
-        }
-    }
-    const void* aL = act_buf(NL);
-    if (pad > 0) {  // x[..., :-pad, :-pad] in front of fc1 (fno2d.py:225-226): the head kernels index flat H W
-        CFD_TRY(cfd_int_pad_crop((const float*)aL, (float*)(base + L.off_crop), (long)B * C, s->H, s->W, pad, stream));
-        aL = base + L.off_crop;
-    }
-    CFD_TRY(cfd_int_fno_head_fwd(aL, mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
-                                 scratch, B, C, s->head, s->out_chan, HW, NL > 0, dt, stream));
+    const View v(p, s, training, dt, ws);
+    const Route rt = route(p, s, v, 0, dt, 0, inputs, mask);  // (flags = 0: this call defers nothing; the trunk reads stem_in_dft)
+    CFD_TRY(trunk(p, s, prm, v, rt, dt, inputs, case_params, mask, stream));
+    const void* aL;
+    CFD_TRY(head_input(s, v, stream, &aL));
+    CFD_TRY(cfd_int_fno_head_fwd(aL, mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums, v.scratch(), s->B, s->hidden,
+                                 s->head, s->out_chan, s->H * s->W, s->num_layers > 0, dt, stream));
     return CFD_OK;
 }
 
@@ -252,68 +293,33 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
                 "cfd_fno_forward_train: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_forward_train: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     const int dt = act_dtype;
-    const Layout L = make_layout(p, s, 1, dt);
-    char* base = (char*)ws;
-    const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
-    const size_t esz = cfd_dt_size(dt);
-    auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)l * L.n_act * esz); };
-    auto xh_buf = [&](int l) { return (float*)(base + L.off_xh) + (size_t)l * L.n_modes; };
-    float* z = (float*)(base + L.off_z);
-    float* gA = (float*)(base + L.off_gA);
-    void* scratch = base + L.off_scratch;
+    const View v(p, s, 1, dt, ws);
+    const Route rt = route(p, s, v, which, dt, flags, inputs, mask);
+    const int B = s->B, C = s->hidden, HW = s->H * s->W, NL = s->num_layers, pad = s->pad;  // HW: the data grid
     // the label's energy and the gradient coefficients: independent of the network (scratch is free until the head); with
     // side_stream bit 1 they run beside the lifting layer on the side stream and join in front of the head (off by default:
     // the fork / join pair costs more than the 16 us it hides -- side.cpp)
-    const Deferred df = deferred(p, s, L, base, which, dt, flags, inputs, mask);
-    hipStream_t side = cfd_side_fork((hipStream_t)stream, df.scale ? 0 : 1);
-    if (!df.scale) CFD_TRY(cfd_label_energy_coef(label, mask, sums, coef, scratch, B, s->out_chan, HW, which, upstream, side));
-    const bool sd = pad == 0 && dt == CFD_DT_F32 && NL >= 1 && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, act_buf(0));
-    if (pad > 0)
-        CFD_TRY(cfd_int_stem_pad(inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), (float*)(base + L.off_coord), B,
-                                 s->in_chan, s->n_case_params, C, s->H, s->W, pad, stream));
-    else if (!sd)
-        CFD_TRY(cfd_int_fno_stem_fwd(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, act_buf(0), B, s->in_chan, s->n_case_params, C,
-                                     dt, stream));
-    for (int l = 0; l < NL; ++l) {  // FnoBlock.forward, fno2d.py:106-112
-        const int act = l > 0;
-        if (l == 0 && sd)
-            CFD_TRY(cfd_int_spectral_dft_stem(p, inputs, mask, case_params, prm->fc0_w, prm->fc0_b, (float*)act_buf(0), xh_buf(0), B,
-                                              s->n_case_params, C, stream));
-        else
-            CFD_TRY(cfd_int_spectral_dft(p, act_buf(l), xh_buf(l), B * C, act, dt, stream));
-        CFD_TRY(cfd_spectral_mix(p, xh_buf(l), prm->spec_w1[l], prm->spec_w2[l], z, B, C, C, 0, stream));
-        if (dt == CFD_DT_F32) {
-            CFD_TRY(cfd_fno_block_fwd(p, (const float*)act_buf(l), z, prm->w0_w[l], prm->w0_b[l], (float*)act_buf(l + 1), B, C, C, act, stream));
-        } else {
-            float* tmp = (float*)(base + L.off_tmp);
-            CFD_TRY(cfd_int_chanmix(act_buf(l), prm->w0_w[l], prm->w0_b[l], tmp, B, C, C, HWp, act, 0, dt, stream));
-            CFD_TRY(cfd_int_spectral_idft(p, z, tmp, nullptr, act_buf(l + 1), B * C, 1, dt, stream));
-        }
-    }
+    hipStream_t side = cfd_side_fork((hipStream_t)stream, rt.scale ? 0 : 1);
+    if (!rt.scale) CFD_TRY(cfd_label_energy_coef(label, mask, sums, coef, v.scratch(), B, s->out_chan, HW, which, upstream, side));
+    CFD_TRY(trunk(p, s, prm, v, rt, dt, inputs, case_params, mask, stream));
     CFD_TRY(cfd_side_join((hipStream_t)stream, side));
     // Domain padding: the head runs on the data grid -- a_L cropped into the compact region, d loss / d a_L written compactly into gB
     // (free until backward phase 1 writes it) and embedded into gA with a zero band: what autograd's slice backward produces.
-    const void* aL = act_buf(NL);
-    float* ga = gA;
-    if (pad > 0) {
-        CFD_TRY(cfd_int_pad_crop((const float*)aL, (float*)(base + L.off_crop), (long)B * C, s->H, s->W, pad, stream));
-        aL = base + L.off_crop;
-        ga = (float*)(base + L.off_gB);
-    }
-    // deferred normaliser: the mse coefficient by value, sum (label*mask)^2 and the count leave the head's reduction (sums[2], sums[3])
-    if (C > 32) {  // wide route: head forward (sums[0..1]; sums[2..3] and coef came from cfd_label_energy_coef), then its backward
-        CFD_TRY(cfd_int_wide_head_fwd((const float*)aL, mask, label, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums,
-                                      scratch, B, C, s->out_chan, HW, NL > 0, stream, 0));
-        CFD_TRY(cfd_int_wide_head_bwd((const float*)aL, mask, label, preds, nullptr, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, ga,
-                                      g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->out_chan, HW, NL > 0, stream));
+    const void* aL;
+    CFD_TRY(head_input(s, v, stream, &aL));
+    float* ga = pad > 0 ? v.gB() : v.gA();
+    if (C > 32) {  // wide route: the two passes behind cfd_int_fno_head_train (sums[2..3] and coef came from cfd_label_energy_coef)
+        CFD_TRY(cfd_int_fno_head_train(aL, mask, label, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums, ga, g->fc1_w, g->fc1_b,
+                                       g->fc2_w, g->fc2_b, v.scratch(), B, C, s->head, s->out_chan, HW, NL > 0, dt, stream));
     } else {
+        // deferred normaliser: the mse coefficient by value, sum (label*mask)^2 and the count leave the head's reduction (sums[2], sums[3])
         const float count = (float)((double)B * s->out_chan * HW);
         HeadTail ht{};
-        CFD_TRY(cfd_int_fno_head_train_f(aL, mask, label, df.scale ? nullptr : coef, upstream / count, 0.f, df.scale ? count : 0.f,
+        CFD_TRY(cfd_int_fno_head_train_f(aL, mask, label, rt.scale ? nullptr : coef, upstream / count, 0.f, rt.scale ? count : 0.f,
                                          prm->fc1_w, prm->fc1_b, prm->fc2_w, prm->fc2_b, preds, sums, ga, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b,
-                                         (char*)scratch + L.head_off, B, C, s->head, s->out_chan, HW, NL > 0, dt, stream, df.head ? &ht : nullptr));
+                                         v.head_rec(), B, C, s->head, s->out_chan, HW, NL > 0, dt, stream, rt.head ? &ht : nullptr));
     }
-    if (pad > 0) CFD_TRY(cfd_int_pad_embed(ga, gA, (long)B * C, s->H, s->W, pad, stream));
+    if (pad > 0) CFD_TRY(cfd_int_pad_embed(ga, v.gA(), (long)B * C, s->H, s->W, pad, stream));
     return CFD_OK;
 }
 
@@ -348,69 +354,47 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     CFD_REQUIRE(prm && g && inputs && ws, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     const int dt = act_dtype;
-    const Layout L = make_layout(p, s, 1, dt);
-    char* base = (char*)ws;
+    const View v(p, s, 1, dt, ws);
     const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
-    const size_t esz = cfd_dt_size(dt);
     CFD_REQUIRE(phase >= 0 && phase <= NL + 1, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: phase %d outside 0..%d", phase, NL + 1);
-    auto act_buf = [&](int l) { return (void*)(base + L.off_acts + (size_t)l * L.n_act * esz); };
-    auto xh_buf = [&](int l) { return (float*)(base + L.off_xh) + (size_t)l * L.n_modes; };
-    float* z = (float*)(base + L.off_z);
-    float* gA = (float*)(base + L.off_gA);
-    float* gB = (float*)(base + L.off_gB);
-    float* gh = (float*)(base + L.off_gh);
-    void* scratch = base + L.off_scratch;
     if (phase == 0) {
         CFD_REQUIRE(dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED, "cfd_fno_backward_phase: phase 0 with bf16 storage (the head ran in cfd_fno_forward_train_ex)");
-        if (pad > 0) {  // the head on the data grid: a_L as the forward call cropped it, the gradient compact in gB, embedded into gA
-            CFD_TRY(cfd_fno_head_bwd((const float*)(base + L.off_crop), mask, label, preds, gpreds_ext, coef, prm->fc1_w, prm->fc1_b,
-                                     prm->fc2_w, gB, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->head, s->out_chan, HW, NL > 0,
-                                     stream));
-            return cfd_int_pad_embed(gB, gA, (long)B * C, s->H, s->W, pad, stream);
-        }
-        return cfd_fno_head_bwd((const float*)act_buf(NL), mask, label, preds, gpreds_ext, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, gA,
-                                g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, scratch, B, C, s->head, s->out_chan, HW, NL > 0,
-                                stream);
+        // Domain padding: the head on the data grid -- a_L as the forward call cropped it, the gradient compact in gB, embedded into gA
+        const float* aL = pad > 0 ? v.crop() : (const float*)v.act(NL);
+        float* ga = pad > 0 ? v.gB() : v.gA();
+        CFD_TRY(cfd_fno_head_bwd(aL, mask, label, preds, gpreds_ext, coef, prm->fc1_w, prm->fc1_b, prm->fc2_w, ga, g->fc1_w, g->fc1_b, g->fc2_w,
+                                 g->fc2_b, v.scratch(), B, C, s->head, s->out_chan, HW, NL > 0, stream));
+        return pad > 0 ? cfd_int_pad_embed(ga, v.gA(), (long)B * C, s->H, s->W, pad, stream) : CFD_OK;
     }
     const int done = phase - 1;  // blocks already processed: the gradient sits in gA after an even count
-    float* gcur = (done & 1) ? gB : gA;
-    float* gnext = (done & 1) ? gA : gB;
-    // Round 5: where the fused FnoBlock kernel runs the last block phase (l = 0), it emits the six per-(entry, channel) sums the lifting
-    // layer's gradient needs instead of storing g_0 for a pass that reads it back (cfd_tail.h: CfdStemG): one activation-sized write and
-    // the k_chan_wgrad_stem launch less.  Both phases evaluate the same predicate.
-    // (Not with domain padding: g_0 lives on the padded grid and the sums would be taken with the plan's coordinates.)
-    const bool stemg = pad == 0 && dt == CFD_DT_F32 && NL >= 1 &&
-                       cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, z);
-    float* stem_part = (float*)((char*)scratch + stemg_offset(p, B, C, HWp));
-    const Deferred df = deferred(p, s, L, base, which, dt, flags, inputs, mask);
-    CFD_REQUIRE(!df.head || sums, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: CFD_TRAIN_DEFER_HEAD needs the `sums` of the forward call");
+    float* gcur = (done & 1) ? v.gB() : v.gA();
+    float* gnext = (done & 1) ? v.gA() : v.gB();
+    const Route rt = route(p, s, v, which, dt, flags, inputs, mask);
+    CFD_REQUIRE(!rt.head || sums, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: CFD_TRAIN_DEFER_HEAD needs the `sums` of the forward call");
     if (phase == NL + 1) {
-        if (stemg && df.stem) return CFD_OK;  // cfd_fno_adam_step's launch finishes the lifting layer's gradient
-        if (stemg)
-            return cfd_int_stemg_combine(p, stem_part, case_params, g->fc0_w, g->fc0_b, B, C, s->in_chan, s->n_case_params, stream);
-        if (pad > 0) {  // g_0 cropped into the free gradient buffer; the lifting layer's gradient on the data grid with ITS coordinates
+        if (rt.stem) return CFD_OK;  // cfd_fno_adam_step's launch finishes the lifting layer's gradient
+        if (rt.stemg) return cfd_int_stemg_combine(p, v.stem_part(), case_params, g->fc0_w, g->fc0_b, B, C, s->in_chan, s->n_case_params, stream);
+        // Domain padding: g_0 cropped into the free gradient buffer; the lifting layer's gradient on the data grid with ITS coordinates
+        const float* g0 = gcur;
+        if (pad > 0) {
             CFD_TRY(cfd_int_pad_crop(gcur, gnext, (long)B * C, s->H, s->W, pad, stream));
-            const cfd_plan dp = data_plan(p, s, (float*)(base + L.off_coord));
-            return cfd_fno_stem_bwd(&dp, gnext, inputs, mask, case_params, g->fc0_w, g->fc0_b, scratch, B, s->in_chan, s->n_case_params, C,
-                                    stream);
+            g0 = gnext;
         }
-        return cfd_fno_stem_bwd(p, gcur, inputs, mask, case_params, g->fc0_w, g->fc0_b, scratch, B, s->in_chan,
-                                s->n_case_params, C, stream);
+        const cfd_plan dp = data_plan(p, s, v.coord());
+        return cfd_fno_stem_bwd(&dp, g0, inputs, mask, case_params, g->fc0_w, g->fc0_b, v.scratch(), B, s->in_chan, s->n_case_params, C, stream);
     }
     const int l = NL - phase;
     const int act = l > 0;
     // gcur = d loss / d a_{l+1}
-    char* scratch2 = (char*)scratch + cfd_align_up(cfd_spectral_wgrad_workspace_bytes(p, B, C, C), 256);
     if (dt == CFD_DT_BF16) {
         // two passes for the input gradient (1x1 conv transposed into the fp32 scratch tensor, inverse transform + addend
         // [* gelu'(a_l), a_l read as bf16]); the weight-gradient producers reduce their own partial sums
-        float* tmp = (float*)(base + L.off_tmp);
-        CFD_TRY(cfd_spectral_dft(p, gcur, gh, B * C, 0, stream));
-        CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, xh_buf(l), gh, prm->spec_w1[l], prm->spec_w2[l], z, g->spec_w1[l],
-                                               g->spec_w2[l], scratch, B, C, C, stream, nullptr));
-        CFD_TRY(cfd_int_chan_wgrad_dt(gcur, act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HWp, act, dt, stream, nullptr));
-        CFD_TRY(cfd_chanmix(gcur, prm->w0_w[l], nullptr, tmp, B, C, C, HWp, 0, 1, stream));
-        return cfd_int_spectral_idft_grad(p, z, tmp, act ? act_buf(l) : nullptr, gnext, B * C, dt, stream);
+        CFD_TRY(cfd_spectral_dft(p, gcur, v.gh(), B * C, 0, stream));
+        CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, v.xh(l), v.gh(), prm->spec_w1[l], prm->spec_w2[l], v.z(), g->spec_w1[l], g->spec_w2[l],
+                                               v.scratch(), B, C, C, stream, nullptr));
+        CFD_TRY(cfd_int_chan_wgrad_dt(gcur, v.act(l), g->w0_w[l], g->w0_b[l], v.scratch2(), B, C, C, HWp, act, dt, stream, nullptr));
+        CFD_TRY(cfd_chanmix(gcur, prm->w0_w[l], nullptr, v.tmp(), B, C, C, HWp, 0, 1, stream));
+        return cfd_int_spectral_idft_grad(p, v.z(), v.tmp(), act ? v.act(l) : nullptr, gnext, B * C, dt, stream);
     }
     // the reductions of both weight gradients ride in front of the input-gradient kernel's launch (cfd_tail.h); whatever
     // a producer could not defer it has already reduced itself.  The 1x1 weight gradient needs only gcur and a_l; with
@@ -419,17 +403,17 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     // takes 53 us instead of 26 -- it needs the wave slots the streaming kernel occupies -- and the phase is no shorter.
     hipStream_t side = cfd_side_fork((hipStream_t)stream, 2);
     CfdReduceTail tail{};
-    CFD_TRY(cfd_int_chan_wgrad(gcur, (const float*)act_buf(l), g->w0_w[l], g->w0_b[l], scratch2, B, C, C, HWp, act, side, &tail.chan));
-    CFD_TRY(cfd_spectral_dft(p, gcur, gh, B * C, 0, stream));
-    CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, xh_buf(l), gh, prm->spec_w1[l], prm->spec_w2[l], z, g->spec_w1[l],
-                                           g->spec_w2[l], scratch, B, C, C, stream, &tail.spec));
+    CFD_TRY(cfd_int_chan_wgrad(gcur, (const float*)v.act(l), g->w0_w[l], g->w0_b[l], v.scratch2(), B, C, C, HWp, act, side, &tail.chan));
+    CFD_TRY(cfd_spectral_dft(p, gcur, v.gh(), B * C, 0, stream));
+    CFD_TRY(cfd_int_spectral_mix_adj_wgrad(p, v.xh(l), v.gh(), prm->spec_w1[l], prm->spec_w2[l], v.z(), g->spec_w1[l], g->spec_w2[l], v.scratch(),
+                                           B, C, C, stream, &tail.spec));
     CFD_TRY(cfd_side_join((hipStream_t)stream, side));  // the block kernel reduces the 1x1 partial sums
-    if (df.head && phase == 1)  // the reduction cfd_fno_forward_train_f left behind (records at head_off: nothing of this phase touched them)
-        tail.head = cfd_int_head_tail((char*)scratch + L.head_off, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, sums, B, C, s->out_chan, HW,
-                                      df.scale ? (float)((double)B * s->out_chan * HW) : 0.f);
+    if (rt.head && phase == 1)  // the reduction cfd_fno_forward_train_f left behind (records at head_rec: nothing of this phase touched them)
+        tail.head = cfd_int_head_tail(v.head_rec(), g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, sums, B, C, s->out_chan, HW,
+                                      rt.scale ? (float)((double)B * s->out_chan * HW) : 0.f);
     tail.nblk = (tail.spec.part || tail.chan.part || tail.head.part) ? 128 : 0;
-    const CfdStemG sg{(l == 0 && stemg) ? inputs : nullptr, mask, p->d_gx, p->d_gy, stem_part, s->in_chan};
-    return cfd_int_fno_block_bwd_input(p, gcur, z, prm->w0_w[l], act ? (const float*)act_buf(l) : nullptr, gnext, B, C, C, stream, &tail, &sg);
+    const CfdStemG sg{(l == 0 && rt.stemg) ? inputs : nullptr, mask, p->d_gx, p->d_gy, v.stem_part(), s->in_chan};
+    return cfd_int_fno_block_bwd_input(p, gcur, v.z(), prm->w0_w[l], act ? (const float*)v.act(l) : nullptr, gnext, B, C, C, stream, &tail, &sg);
 }
 
 extern "C" int cfd_fno_backward(const cfd_plan* p, const cfd_fno_shape* s, const cfd_fno_params* prm,
@@ -453,13 +437,11 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     CFD_TRY(check_shape("cfd_fno_adam_step", p, s, act_dtype));
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
-    const Layout L = make_layout(p, s, 1, act_dtype);
-    char* base = (char*)ws;
-    const Deferred df = deferred(p, s, L, base, which, act_dtype, flags, inputs, mask);
-    CFD_REQUIRE(!df.scale || sums, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_TRAIN_DEFER_SCALE needs the `sums` of the forward call");
+    const View v(p, s, 1, act_dtype, ws);
+    const Route rt = route(p, s, v, which, act_dtype, flags, inputs, mask);
+    CFD_REQUIRE(!rt.scale || sums, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_TRAIN_DEFER_SCALE needs the `sums` of the forward call");
     StemAdamJob job{};
-    if (df.stem) {
-        const int B = s->B, C = s->hidden, HW = s->H * s->W;
+    if (rt.stem) {
         CFD_REQUIRE(case_params || s->n_case_params == 0, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL case_params");
         const float* gw = (const float*)g->fc0_w;
         const float* gb = (const float*)g->fc0_b;
@@ -467,10 +449,9 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
                     "cfd_fno_adam_step: grads->fc0 does not point into the flat gradient buffer");
         CFD_REQUIRE((const float*)prm->fc0_w - param == gw - grad && (const float*)prm->fc0_b - param == gb - grad, CFD_ERR_INVALID_ARG,
                     "cfd_fno_adam_step: params and grads are laid out differently");
-        const int spl = cfd_int_stemg_splits(p, B);
-        job = StemAdamJob{(const float*)(base + L.off_scratch + stemg_offset(p, B, C, HW)), case_params, B * spl, spl, s->n_case_params,
-                          s->in_chan, C, (long)(gw - grad), (long)(gb - grad)};
+        const int spl = cfd_int_stemg_splits(p, s->B);
+        job = StemAdamJob{v.stem_part(), case_params, s->B * spl, spl, s->n_case_params, s->in_chan, s->hidden, (long)(gw - grad), (long)(gb - grad)};
     }
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                               df.scale ? sums : nullptr, df.stem ? &job : nullptr, stream);
+                               rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, stream);
 }

@@ -17,7 +17,6 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
-from ._capi import FnoShape
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
@@ -295,12 +294,7 @@ class FnoTrainEngine:
         # launch).  Data-parallel steps keep them: a rank's gradients must be final and normalised by ITS labels before the all-reduce.
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
         self.defer_flags = 0 if (self.sync.exchange or not fused_head) else 7
-        # the wide-channel route (hidden > 32), the many-modes route (modes1 > 15 or modes2 > 16, or a grid wider than 80 columns: known
-        # per batch, _prepare) and the head's channel route (out_chan > 2) have none of the fused kernels and ignore the flags (fno.cpp:
-        # deferred()): their gradients are final after the pass
-        self._model_defers = (self.cfg["hidden"] <= 32 and self.cfg["modes1"] <= 15 and self.cfg["modes2"] <= 16
-                              and self.cfg["out_chan"] <= 2)
-        self._route_defers = self._model_defers
+        self._route_defers = False  # whether the batch's route honours the flags: known per batch (_prepare, _lib.fno_call)
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.scores_buf = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -314,11 +308,7 @@ class FnoTrainEngine:
         if key == self._shape_key:
             return
         c = self.cfg
-        pad = int(c.get("padding", 0))  # Fno2d(padding=): the plan is the padded grid's; a padded shape defers nothing (fno.cpp: deferred())
-        self._route_defers = self._model_defers and W + pad <= 80 and pad == 0  # (cfd_plan_create: every plan with W > 80 is a many-modes plan)
-        self.plan = _lib.plan(H + pad, W + pad, c["modes1"], c["modes2"], self.device.index)
-        self.shape = FnoShape(B, H, W, in_chan, c["out_chan"], case_params.shape[1], c["hidden"], self.L, c["modes1"],
-                              c["modes2"], c["head"], pad)
+        self.plan, self.shape, self._route_defers = _lib.fno_call(c, B, in_chan, H, W, case_params.shape[1], self.device)
         nbytes = self.api.size("cfd_fno_workspace_bytes_ex", self.plan, ctypes.byref(self.shape), 1, self.act_dtype)
         if nbytes == 0:
             raise RuntimeError("cfd_fno_workspace_bytes_ex returned 0 for this shape / activation type")
@@ -330,31 +320,34 @@ class FnoTrainEngine:
     def forward_backward(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None, flags: int = 0):
         """Enqueue forward + loss + backward into the flat gradient buffer (every gradient is overwritten).  ``flags`` =
         CFD_TRAIN_DEFER_* (train_step passes ``defer_flags``): the gradients are then complete only after ``optimizer_step``'s launch."""
+        a = self.api
+        model, data, sums, coef, ws, st = self._begin(inputs, label, case_params, mask, flags)
+        if self.fused_head:
+            a.call("cfd_fno_forward_train_f", *model, *data, sums, coef, ws, self.loss_id, 1.0, self.act_dtype, flags, st)
+            for phase in range(1, self.L + 2):  # phase 0 (the head) left the fused kernel already
+                a.call("cfd_fno_backward_phase_f", *model, *data, None, coef, sums, ws, phase, self.loss_id, self.act_dtype, flags, st)
+            return
+        if flags:
+            raise RuntimeError("FnoTrainEngine: the deferred training step needs the one-pass head (fused_head)")
+        self._forward_two_pass_head(model, data, sums, coef, ws, st)
+        a.call("cfd_fno_backward", *model, *data, None, coef, ws, st)
+
+    def _begin(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor], flags: int):
+        """What every pass starts with: the tensor check, the per-shape state, and the arguments its C calls share --
+        (plan, shape, params, grads), (inputs, case_params, mask, label, preds), sums, coef, workspace, stream."""
         for t in (inputs, label, case_params, mask):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
                 raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
         self._prepare(inputs, case_params)
-        st = torch.cuda.current_stream().cuda_stream
-        a, sp = self.api, ctypes.byref(self.shape)
-        mp = None if mask is None else mask.data_ptr()
         self._last = (inputs, case_params, mask, flags)  # optimizer_step finishes what the flags deferred
-        if self.fused_head:
-            a.call("cfd_fno_forward_train_f", self.plan, sp, ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
-                   inputs.data_ptr(), case_params.data_ptr(), mp, label.data_ptr(), self.preds.data_ptr(), self.sums.data_ptr(),
-                   self.coef.data_ptr(), self.ws.data_ptr(), self.loss_id, 1.0, self.act_dtype, flags, st)
-            for phase in range(1, self.L + 2):  # phase 0 (the head) left the fused kernel already
-                a.call("cfd_fno_backward_phase_f", self.plan, sp, ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
-                       inputs.data_ptr(), case_params.data_ptr(), mp, label.data_ptr(), self.preds.data_ptr(), None,
-                       self.coef.data_ptr(), self.sums.data_ptr(), self.ws.data_ptr(), phase, self.loss_id, self.act_dtype, flags, st)
-            return
-        if flags:
-            raise RuntimeError("FnoTrainEngine: the deferred training step needs the one-pass head (fused_head)")
-        a.call("cfd_fno_forward", self.plan, sp, ctypes.byref(self.pstruct), inputs.data_ptr(), case_params.data_ptr(), mp,
-               label.data_ptr(), self.preds.data_ptr(), self.sums.data_ptr(), self.ws.data_ptr(), 1, st)
-        a.call("cfd_loss_coef", self.sums.data_ptr(), self.coef.data_ptr(), self.loss_id, 1.0, st)
-        a.call("cfd_fno_backward", self.plan, sp, ctypes.byref(self.pstruct), ctypes.byref(self.gstruct), inputs.data_ptr(),
-               case_params.data_ptr(), mp, label.data_ptr(), self.preds.data_ptr(), None, self.coef.data_ptr(),
-               self.ws.data_ptr(), st)
+        model = (self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct))
+        data = (inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), label.data_ptr(), self.preds.data_ptr())
+        return (model, data, self.sums.data_ptr(), self.coef.data_ptr(), self.ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+    def _forward_two_pass_head(self, model, data, sums, coef, ws, st):
+        """fused_head = False: the plain forward (which keeps the activations), then the loss coefficients from its sums."""
+        self.api.call("cfd_fno_forward", *model[:3], *data, sums, ws, 1, st)
+        self.api.call("cfd_loss_coef", sums, coef, self.loss_id, 1.0, st)
 
     # ---- data-parallel step: backward phase by phase, each phase's gradient slice reduced while the next computes ----
     def phase_slices(self) -> List[Tuple[int, int]]:
@@ -370,28 +363,17 @@ class FnoTrainEngine:
         while the following phases compute (the head's 12 KB first, then one 0.9-MB bucket per FnoBlock, during the next
         block's DFT / mix / fused block kernels).  Returns the 1/world scale for Adam.  Bitwise the same gradients as
         forward_backward + GradSync.all_reduce (same kernels, same reduction per element)."""
-        for t in (inputs, label, case_params, mask):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
-        self._prepare(inputs, case_params)
-        self._last = (inputs, case_params, mask, 0)  # (a data-parallel pass defers nothing: optimizer_step runs the plain flat Adam)
-        st = torch.cuda.current_stream().cuda_stream
-        a, sp = self.api, ctypes.byref(self.shape)
-        mp = None if mask is None else mask.data_ptr()
+        a = self.api
+        # (flags = 0: a data-parallel pass defers nothing, optimizer_step runs the plain flat Adam)
+        model, data, sums, coef, ws, st = self._begin(inputs, label, case_params, mask, 0)
         if self.fused_head:
-            a.call("cfd_fno_forward_train_ex", self.plan, sp, ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
-                   inputs.data_ptr(), case_params.data_ptr(), mp, label.data_ptr(), self.preds.data_ptr(), self.sums.data_ptr(),
-                   self.coef.data_ptr(), self.ws.data_ptr(), self.loss_id, 1.0, self.act_dtype, st)
+            a.call("cfd_fno_forward_train_ex", *model, *data, sums, coef, ws, self.loss_id, 1.0, self.act_dtype, st)
         else:
-            a.call("cfd_fno_forward", self.plan, sp, ctypes.byref(self.pstruct), inputs.data_ptr(), case_params.data_ptr(), mp,
-                   label.data_ptr(), self.preds.data_ptr(), self.sums.data_ptr(), self.ws.data_ptr(), 1, st)
-            a.call("cfd_loss_coef", self.sums.data_ptr(), self.coef.data_ptr(), self.loss_id, 1.0, st)
+            self._forward_two_pass_head(model, data, sums, coef, ws, st)
         handles = []
         for phase, (s0, s1) in enumerate(self.phase_slices()):
             if not (self.fused_head and phase == 0):  # the fused forward has produced the head's gradients already
-                a.call("cfd_fno_backward_phase_ex", self.plan, sp, ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
-                       inputs.data_ptr(), case_params.data_ptr(), mp, label.data_ptr(), self.preds.data_ptr(), None,
-                       self.coef.data_ptr(), self.ws.data_ptr(), phase, self.act_dtype, st)
+                a.call("cfd_fno_backward_phase_ex", *model, *data, None, coef, ws, phase, self.act_dtype, st)
             handles.append(self.sync.reduce_slice_async(self.flat.grad, s0, s1))
         return self.sync.wait_all(handles)
 

@@ -12,7 +12,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._capi import FnoParams, FnoShape
+from ._capi import FnoParams
 
 
 def _require_cuda(*ts: Optional[Tensor]):
@@ -320,7 +320,7 @@ class FnoForwardFn(torch.autograd.Function):
                 *params: Tensor):
         _require_cuda(inputs, case_params, mask, label, *params)
         api = _lib.api()
-        L, C, m1, m2, head = cfg["num_layers"], cfg["hidden"], cfg["modes1"], cfg["modes2"], cfg["head"]
+        L = cfg["num_layers"]
         inputs, case_params, mask, label = _f32c(inputs), _f32c(case_params), _f32c(mask), _f32c(label)
         B, in_chan, H, W = inputs.shape
         out_chan = cfg["out_chan"]
@@ -329,9 +329,7 @@ class FnoForwardFn(torch.autograd.Function):
             raise RuntimeError(f"FnoForwardFn: expected {6 + 4 * L} parameter tensors, got {len(params)}")
         if params[0].shape[1] != in_chan + 3 + P:
             raise RuntimeError(f"Fno2d: fc0 expects {params[0].shape[1]} features but inputs provide {in_chan}+3+{P}")
-        pad = int(cfg.get("padding", 0))  # Fno2d(padding=): the blocks run on (H + pad, W + pad), which is the grid the plan is for
-        plan = _lib.plan(H + pad, W + pad, m1, m2, inputs.device.index)
-        shape = FnoShape(B, H, W, in_chan, out_chan, P, C, L, m1, m2, head, pad)
+        plan, shape, _ = _lib.fno_call(cfg, B, in_chan, H, W, P, inputs.device)
         flat = [(_creal(p.detach()) if p.is_complex() else _f32c(p.detach())) for p in params]
         pstruct = _param_struct([t.data_ptr() for t in flat], L)
         # needs_input_grad reflects requires_grad whatever the grad mode is (and grad mode is always off inside

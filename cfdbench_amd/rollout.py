@@ -12,7 +12,6 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._capi import FnoShape
 from .functional import _creal, _param_struct
 
 
@@ -37,10 +36,7 @@ class FnoRollout:
         cfg = self.model.abi_config()
         if c != cfg["out_chan"]:
             raise RuntimeError("rollout feeds predictions back as inputs: in_chan must equal out_chan")
-        pad = int(cfg.get("padding", 0))  # Fno2d(padding=): the plan is the padded grid's (bf16 storage: the library refuses)
-        plan = _lib.plan(H + pad, W + pad, cfg["modes1"], cfg["modes2"], device.index)
-        shape = FnoShape(B, H, W, c, cfg["out_chan"], P, cfg["hidden"], cfg["num_layers"], cfg["modes1"], cfg["modes2"],
-                         cfg["head"], pad)
+        plan, shape, _ = _lib.fno_call(cfg, B, c, H, W, P, device)  # (Fno2d(padding=) with bf16 storage: the library refuses)
         st = dict(plan=plan, shape=shape,
                   frames=torch.empty((steps + 1, B, c, H, W), dtype=torch.float32, device=device),
                   cp=torch.empty((B, P), dtype=torch.float32, device=device),

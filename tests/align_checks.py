@@ -28,6 +28,7 @@ import numpy as np
 from cfdbench_amd._capi import CfdError
 from tests import backends as BK
 from tests import chan_checks as CK
+from tests import fno_checks as F
 from tests import kernel_checks as K
 from tests import modes_checks as MK
 from tests import wide_checks as WK
@@ -154,7 +155,7 @@ def check_fno_train_phases(be, ex, B=1, C=8, L=1, H=64, W=64, p=5, which="nmse",
         shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
         gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
+        ps, gs = F.make_param_struct(be, pd, L), F.make_param_struct(be, gd, L)
         ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
         preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
@@ -467,8 +468,8 @@ def _calls_of(fn, seen=None):
     names = set(re.findall(r"""["'](cfd_\w+)["']""", src))
     names |= {n + "_ex" for n in names if f'"{n}" + sfx' in src}
     mod = sys.modules[fn.__module__]
-    for helper in set(re.findall(r"\b([A-Za-z_]\w*)\(", src)) | set(re.findall(r"\b(?:K|WK|MK|CK)\.(\w+)\(", src)):
-        for m in (mod, K):
+    for helper in set(re.findall(r"\b([A-Za-z_]\w*)\(", src)) | set(re.findall(r"\b(?:K|WK|MK|CK|F)\.(\w+)\(", src)):
+        for m in (mod, K, F):
             h = getattr(m, helper, None)
             if inspect.isfunction(h) and h.__module__.startswith("tests.") and h.__name__ != "tuned":
                 names |= _calls_of(h, seen)

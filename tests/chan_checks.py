@@ -12,6 +12,7 @@ import numpy as np
 from cfdbench_amd._capi import CfdError, FnoShape
 from oracle import fno_oracle as O
 from oracle import synth
+from tests import fno_checks as F
 from tests import kernel_checks as K
 from tests.backends import POISON_WORD
 
@@ -191,44 +192,11 @@ def check_stem(be, B, H, W, P_, C, cin, border=True, seed=3):
         api.plan_destroy(plan)
 
 
-def run_fno(be, params, batch, L, C, H, W, p, m1=12, m2=12, which="nmse"):
-    """cfd_fno_forward (training workspace) + cfd_loss_coef + cfd_fno_backward, then the inference workspace; the channel counts come
-    from the batch (K.run_fno fixes 2 / 2)."""
-    api, P = be.api, be.ptr
-    B, cin = batch["inputs"].shape[:2]
-    cout = batch["label"].shape[1]
-    plan = api.plan_create(H, W, m1, m2)
-    try:
-        shape = FnoShape(B, H, W, cin, cout, p, C, L, m1, m2, 128)
-        sh = ctypes.byref(shape)
-        pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
-        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        preds, sums, coef, scores = be.out((B, cout, H, W)), be.out((4,)), be.out((2,)), be.out((4,))
-        api.call("cfd_fno_forward", plan, sh, ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(ws), 1, be.stream)
-        api.call("cfd_loss_coef", P(sums), P(coef), WHICH[which], 1.0, be.stream)
-        api.call("cfd_fno_backward", plan, sh, ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef),
-                 P(ws), be.stream)
-        api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
-        be.sync()
-        out = dict(grads={k: be.host(v) for k, v in gd.items()}, scores=be.host(scores), sums=be.host(sums), preds=be.host(preds))
-        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 0))
-        preds0 = be.out((B, cout, H, W))
-        api.call("cfd_fno_forward", plan, sh, ctypes.byref(ps), P(di), P(dc), P(dm), None, P(preds0), None, P(ws0), 0, be.stream)
-        be.sync()
-        out["preds_infer"] = be.host(preds0)
-        return out
-    finally:
-        api.plan_destroy(plan)
-
-
 def check_fno_vs_oracle(be, B, C, L, H, W, cin, cout, p=5, m1=12, m2=12, border=True, gain=4.0, pseed=7, bseed=8):
     """Whole model: predictions (both workspaces), the four scores and every parameter gradient against the fp64 oracle."""
     params = make_params(pseed, C, L, m1, m2, p, cin, cout, gain)
     batch = make_batch(bseed, B, H, W, p, cin, cout, border)
-    out = run_fno(be, params, batch, L, C, H, W, p, m1, m2)
+    out = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2)
     p64, b64 = _to64(params, batch)
     ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
     rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], "nmse"), L)
@@ -244,58 +212,20 @@ def check_fno_train_step(be, B, C, L, H, W, cin, cout, p=5, which="nmse", flags=
     """K.check_fno_train_step_deferred at any channel counts: the fused step (cfd_fno_forward_train_f, the backward phases,
     cfd_fno_adam_step) with `flags` against flags = 0 -- parameters after `steps` steps, predictions, sums, the first gradient -- and
     the first gradient of the flagged run (every tensor) against the oracle."""
-    api, P = be.api, be.ptr
-    wid = WHICH[which]
     params = make_params(pseed, C, L, 12, 12, p, cin, cout, 4.0)
     batch = make_batch(bseed, B, H, W, p, cin, cout, border)
-    layout, off = {}, 0
-    for k, v in params.items():
-        n = v.size * (2 if np.iscomplexobj(v) else 1)
-        layout[k] = (off, n)
-        off += (n + 3) // 4 * 4
-    numel = off
-    flat0 = np.zeros(numel, np.float32)
-    for k, v in params.items():
-        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
-    plan = api.plan_create(H, W, 12, 12)
-    try:
-        shape = FnoShape(B, H, W, cin, cout, p, C, L, 12, 12, 128)
-        sh = ctypes.byref(shape)
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        out = {}
+    # (out_chan > 2 defers nothing: the buffer holds the loss's own gradient whatever the flags say)
+    out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, which=which, flags=flags, steps=steps)
+    a, b = out[0], out[flags]
+    res = {"params": nm(b["flat"], a["flat"]), "preds": nm(b["preds1"], a["preds1"]), "grad_vs_immediate": nm(b["g1"], a["g1"]),
+           "sums": float(np.max(np.abs(b["sums1"] - a["sums1"]) / np.abs(a["sums1"])))}
+    p64, b64 = _to64(params, batch)
+    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
+    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
+    for k in params:
         for fl in (0, flags):
-            flat, grad = be.dev(flat0), K.flat_grad_buffer(be, layout, numel)
-            m, v = be.zeros((numel,)), be.zeros((numel,))
-            ps, gs = K._flat_struct(be, flat, layout, L), K._flat_struct(be, grad, layout, L)
-            pr, gr = ctypes.byref(ps), ctypes.byref(gs)
-            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
-            preds, sums, coef = be.out((B, cout, H, W)), be.out((4,)), be.out((2,))
-            for step in range(1, steps + 1):
-                api.call("cfd_fno_forward_train_f", plan, sh, pr, gr, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(coef), P(ws), wid,
-                         1.0, 0, fl, be.stream)
-                for phase in range(1, L + 2):
-                    api.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(sums),
-                             P(ws), phase, wid, 0, fl, be.stream)
-                api.call("cfd_fno_adam_step", plan, sh, pr, gr, P(di), P(dc), P(dm), P(sums), P(ws), P(flat), P(grad), P(m), P(v), numel,
-                         1e-3, 0.9, 0.999, 1e-8, 0.0, step, 1.0, wid, 0, fl, be.stream)
-                be.sync()
-                if step == 1:  # out_chan > 2 defers nothing: the buffer holds the loss's own gradient whatever the flags say
-                    out[fl] = dict(g1=be.host(grad).copy(), sums1=be.host(sums).copy(), preds1=be.host(preds).copy())
-            out[fl]["flat"] = be.host(flat).copy()
-        a, b = out[0], out[flags]
-        res = {"params": nm(b["flat"], a["flat"]), "preds": nm(b["preds1"], a["preds1"]), "grad_vs_immediate": nm(b["g1"], a["g1"]),
-               "sums": float(np.max(np.abs(b["sums1"] - a["sums1"]) / np.abs(a["sums1"])))}
-        p64, b64 = _to64(params, batch)
-        ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
-        rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
-        for k in params:
-            want = rg[k]
-            want = (np.stack([want.real, want.imag], -1) if np.iscomplexobj(want) else want).reshape(-1)
-            for fl in (0, flags):
-                res[f"oracle{fl}:" + k] = nm(out[fl]["g1"][layout[k][0]:layout[k][0] + layout[k][1]], want)
-        return res
-    finally:
-        api.plan_destroy(plan)
+            res[f"oracle{fl}:" + k] = nm(F.flat_slice(out[fl]["g1"], layout, k), F.flat_view(rg[k]))
+    return res
 
 
 def _still_poisoned(be, buf):
@@ -316,7 +246,7 @@ def check_refusals(be, C=20, B=1, H=24, W=26, L=1, p=5):
             sh = ctypes.byref(shape)
             pd = {k: be.dev(v) for k, v in params.items()}
             gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-            ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
+            ps, gs = F.make_param_struct(be, pd, L), F.make_param_struct(be, gd, L)
             pr, gr = ctypes.byref(ps), ctypes.byref(gs)
             di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
             ws = be.scratch(1 << 22)  # (the size functions answer for refused shapes too; any workspace will do: nothing may touch it)

@@ -7,9 +7,11 @@ import ctypes
 
 import numpy as np
 
-from cfdbench_amd._capi import FnoParams, FnoShape
+from cfdbench_amd._capi import FnoShape
 from oracle import fno_oracle as O
 from oracle import synth
+from tests import fno_checks as F
+from tests.fno_checks import flat_grad_buffer, make_param_struct, run_fno
 
 # north_star tolerance: relative nMSE <= 1e-5 (fp32).  The kernels are exact-fp32 MFMA/FMA chains, so the
 # checks hold them to a far tighter bound; TOL is what a fp32 pipeline of this depth can actually deliver.
@@ -427,154 +429,28 @@ def check_loss_and_adam(be, n=10007, seed=5):
     return res
 
 
-def make_param_struct(be, params_dev, L):
-    s = FnoParams()
-    P = be.ptr
-    s.fc0_w, s.fc0_b = P(params_dev["fc0.weight"]), P(params_dev["fc0.bias"])
-    for l in range(L):
-        s.spec_w1[l] = P(params_dev[f"blocks.{l}.conv0.weights1"])
-        s.spec_w2[l] = P(params_dev[f"blocks.{l}.conv0.weights2"])
-        s.w0_w[l] = P(params_dev[f"blocks.{l}.w0.weight"])
-        s.w0_b[l] = P(params_dev[f"blocks.{l}.w0.bias"])
-    s.fc1_w, s.fc1_b = P(params_dev["fc1.weight"]), P(params_dev["fc1.bias"])
-    s.fc2_w, s.fc2_b = P(params_dev["fc2.weight"]), P(params_dev["fc2.bias"])
-    return s
-
-
-def run_fno(be, params, batch, L, C, H, W, p, with_label=True, which="nmse"):
-    """Whole-model forward (+ backward) through cfd_fno_forward / cfd_fno_backward; returns host arrays."""
-    api, P = be.api, be.ptr
-    B = batch["inputs"].shape[0]
-    plan = api.plan_create(H, W, 12, 12)
-    try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
-        pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = make_param_struct(be, pd, L), make_param_struct(be, gd, L)
-        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-        di, dc, dm = be.dev(batch["inputs"]), be.dev(batch["case_params"]), be.dev(batch["mask"])
-        dl = be.dev(batch["label"]) if with_label else None
-        preds = be.out((B, 2, H, W))
-        sums = be.out((4,))
-        api.call("cfd_fno_forward", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds),
-                 P(sums), P(ws), 1, be.stream)
-        out = {}
-        if with_label:
-            coef = be.out((2,))
-            api.call("cfd_loss_coef", P(sums), P(coef), {"mse": 0, "nmse": 1, "mae": 2}[which], 1.0, be.stream)
-            api.call("cfd_fno_backward", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm),
-                     P(dl), P(preds), None, P(coef), P(ws), be.stream)
-            scores = be.out((4,))
-            api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
-            be.sync()
-            out["grads"] = {k: be.host(v) for k, v in gd.items()}
-            out["scores"] = be.host(scores)
-        be.sync()
-        out["preds"] = be.host(preds)
-        # inference-mode workspace (ping-pong activations) must give the same predictions
-        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
-        preds0 = be.out((B, 2, H, W))
-        api.call("cfd_fno_forward", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), None, P(preds0), None,
-                 P(ws0), 0, be.stream)
-        be.sync()
-        out["preds_infer"] = be.host(preds0)
-        return out
-    finally:
-        api.plan_destroy(plan)
-
-
-def flat_grad_buffer(be, layout, numel):
-    """The flat gradient buffer of the fused training step, hostile where the contract allows: every tensor's elements are poisoned
-    (cfdbench_amd.h, cfd_fno_backward: "every tensor overwritten"), the alignment padding between tensors is zero (cfd_fno_adam_step:
-    "elements of the flat buffers that belong to no tensor are read and updated like any other: the caller zeroes them once")."""
-    from tests.backends import poison
-    g = poison((numel,)).copy()
-    used = np.zeros(numel, bool)
-    for off, n in layout.values():
-        used[off:off + n] = True
-    g[~used] = 0.0
-    return be.dev(g)
-
-
-def _flat_struct(be, flat, layout, L):
-    """cfd_fno_params whose tensors are slices of one flat float32 buffer (the training engine's layout)."""
-    base = be.ptr(flat)
-    s = FnoParams()
-    at = lambda k: base + 4 * layout[k][0]  # noqa: E731
-    s.fc0_w, s.fc0_b = at("fc0.weight"), at("fc0.bias")
-    for l in range(L):
-        s.spec_w1[l], s.spec_w2[l] = at(f"blocks.{l}.conv0.weights1"), at(f"blocks.{l}.conv0.weights2")
-        s.w0_w[l], s.w0_b[l] = at(f"blocks.{l}.w0.weight"), at(f"blocks.{l}.w0.bias")
-    s.fc1_w, s.fc1_b, s.fc2_w, s.fc2_b = at("fc1.weight"), at("fc1.bias"), at("fc2.weight"), at("fc2.bias")
-    return s
-
-
 def check_fno_train_step_deferred(be, B, C, L, H, W, p=5, which="nmse", flags=7, steps=2, border=True, pseed=27, bseed=28):
     """Round 6: the fused single-GPU training step with its three tiny launches folded into others (CFD_TRAIN_DEFER_*:
     cfd_fno_forward_train_f / cfd_fno_backward_phase_f / cfd_fno_adam_step) against the same calls with flags = 0 (the label-energy pair,
     the head's own reduction, the fc0 combine, cfd_adam_flat) -- parameters after `steps` Adam steps, predictions, loss sums, and the
     first step's gradient (rescaled by n / sum (label*mask)^2 where the normaliser was deferred) against the fp64 oracle."""
-    api, P = be.api, be.ptr
-    wid = {"mse": 0, "nmse": 1, "mae": 2}[which]
     params = synth.make_fno_params(pseed, C, L, 12, 12, p, spectral_gain=4.0)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=border)
-    names = ["fc0.weight", "fc0.bias"] + [f"blocks.{l}.{t}" for l in range(L) for t in ("conv0.weights1", "conv0.weights2", "w0.weight", "w0.bias")] \
-        + ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-    layout, off = {}, 0
-    for k in names:
-        n = params[k].size * (2 if np.iscomplexobj(params[k]) else 1)
-        layout[k] = (off, n)
-        off += (n + 3) // 4 * 4
-    numel = off
-    flat0 = np.zeros(numel, np.float32)
-    for k in names:
-        v = params[k]
-        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
-    plan = api.plan_create(H, W, 12, 12)
-    try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
-        di, dc, dm, dl = be.dev(batch["inputs"]), be.dev(batch["case_params"]), be.dev(batch["mask"]), be.dev(batch["label"])
-        out = {}
-        for fl in (0, flags):
-            flat, grad = be.dev(flat0), flat_grad_buffer(be, layout, numel)
-            # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
-            m, v = be.zeros((numel,)), be.zeros((numel,))
-            ps, gs = _flat_struct(be, flat, layout, L), _flat_struct(be, grad, layout, L)
-            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-            preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
-            g1 = None
-            for step in range(1, steps + 1):
-                api.call("cfd_fno_forward_train_f", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm), P(dl),
-                         P(preds), P(sums), P(coef), P(ws), wid, 1.0, 0, fl, be.stream)
-                for phase in range(1, L + 2):
-                    api.call("cfd_fno_backward_phase_f", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm),
-                             P(dl), P(preds), None, P(coef), P(sums), P(ws), phase, wid, 0, fl, be.stream)
-                api.call("cfd_fno_adam_step", plan, ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs), P(di), P(dc), P(dm), P(sums), P(ws),
-                         P(flat), P(grad), P(m), P(v), numel, 1e-3, 0.9, 0.999, 1e-8, 0.0, step, 1.0, wid, 0, fl, be.stream)
-                be.sync()
-                if step == 1:
-                    g1 = be.host(grad).copy()
-                    s1 = be.host(sums).copy()
-                    if (fl & 1) and which == "nmse":
-                        g1 = g1 * (s1[3] / s1[2])
-                    out[fl] = dict(g1=g1, sums1=s1, preds1=be.host(preds).copy())
-            out[fl]["flat"] = be.host(flat).copy()
-        a, b = out[0], out[flags]
-        res = {"params": nm(b["flat"], a["flat"]), "preds": nm(b["preds1"], a["preds1"]), "grad_vs_immediate": nm(b["g1"], a["g1"]),
-               "sums": float(np.max(np.abs(b["sums1"] - a["sums1"]) / np.abs(a["sums1"])))}
-        # the deferred step's first gradient against the oracle
-        p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
-        b64 = {k: v.astype(f64) for k, v in batch.items()}
-        ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
-        rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
-        for k in ("fc0.weight", "fc0.bias", "fc1.weight", "fc2.bias", f"blocks.{L - 1}.conv0.weights1" if L else "fc1.bias"):
-            got = b["g1"][layout[k][0]:layout[k][0] + layout[k][1]]
-            want = rg[k]
-            want = (np.stack([want.real, want.imag], -1) if np.iscomplexobj(want) else want).reshape(-1)
-            res["oracle:" + k] = nm(got, want)
-        return res
-    finally:
-        api.plan_destroy(plan)
+    out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, which=which, flags=flags, steps=steps)
+    for fl, o in out.items():  # where the normaliser was deferred the buffer holds the gradient of sum d^2 / n
+        if (fl & 1) and which == "nmse":
+            o["g1"] = o["g1"] * (o["sums1"][3] / o["sums1"][2])
+    a, b = out[0], out[flags]
+    res = {"params": nm(b["flat"], a["flat"]), "preds": nm(b["preds1"], a["preds1"]), "grad_vs_immediate": nm(b["g1"], a["g1"]),
+           "sums": float(np.max(np.abs(b["sums1"] - a["sums1"]) / np.abs(a["sums1"])))}
+    # the deferred step's first gradient against the oracle
+    p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
+    b64 = {k: v.astype(f64) for k, v in batch.items()}
+    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
+    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
+    for k in ("fc0.weight", "fc0.bias", "fc1.weight", "fc2.bias", f"blocks.{L - 1}.conv0.weights1" if L else "fc1.bias"):
+        res["oracle:" + k] = nm(F.flat_slice(b["g1"], layout, k), F.flat_view(rg[k]))
+    return res
 
 
 def check_stem_dft_fusion(be, B, C, L, p, border, seed=61):
@@ -1528,40 +1404,19 @@ def case_fno_train_step(be, ar, B, C, L, H=64, W=64, m1=12, m2=12, p=5, flags=0,
     """The fused training step (cfd_fno_forward_train_f / cfd_fno_backward_phase_f / cfd_fno_adam_step) for `steps` steps: predictions,
     loss sums, the last gradient and the parameters after the steps.  Parameters, gradient and moments are the caller's state (fresh
     per run); predictions, sums, coef and the workspace come from the arena."""
-    api, P = be.api, be.ptr
-    wid = {"mse": 0, "nmse": 1, "mae": 2}[which]
+    api = be.api
     params, d = _fno_setup(be, B, C, L, H, W, m1, m2, p, seed)
-    names = ["fc0.weight", "fc0.bias"] + [f"blocks.{l}.{t}" for l in range(L) for t in ("conv0.weights1", "conv0.weights2", "w0.weight", "w0.bias")] \
-        + ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-    layout, off = {}, 0
-    for k in names:
-        n = params[k].size * (2 if np.iscomplexobj(params[k]) else 1)
-        layout[k] = (off, n)
-        off += (n + 3) // 4 * 4
-    flat0 = np.zeros(off, np.float32)
-    for k in names:
-        v = params[k]
-        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
+    layout, off, flat0 = F.flat_layout(params, L)
     plan = api.plan_create(H, W, m1, m2)
     try:
         shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
-        sh = ctypes.byref(shape)
         flat, grad = be.dev(flat0), flat_grad_buffer(be, layout, off)
         # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
         m, v = be.zeros((off,)), be.zeros((off,))
-        ps, gs = _flat_struct(be, flat, layout, L), _flat_struct(be, grad, layout, L)
-        pr, gr = ctypes.byref(ps), ctypes.byref(gs)
-        ws = ar.scratch(max(api.size("cfd_fno_workspace_bytes", plan, sh, 1), ws_min))
+        ws = ar.scratch(max(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1), ws_min))
         preds, sums, coef = ar.out((B, 2, H, W)), ar.out((4,)), ar.out((2,))
-        a = (P(d["inputs"]), P(d["case_params"]), P(d["mask"]))
-        for step in range(1, steps + 1):
-            api.call("cfd_fno_forward_train_f", plan, sh, pr, gr, *a, P(d["label"]), P(preds), P(sums), P(coef), P(ws), wid, 1.0, 0, flags,
-                     be.stream)
-            for phase in range(1, L + 2):
-                api.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *a, P(d["label"]), P(preds), None, P(coef), P(sums), P(ws), phase, wid,
-                         0, flags, be.stream)
-            api.call("cfd_fno_adam_step", plan, sh, pr, gr, *a, P(sums), P(ws), P(flat), P(grad), P(m), P(v), off, 1e-3, 0.9, 0.999, 1e-8,
-                     0.0, step, 1.0, wid, 0, flags, be.stream)
+        F.fused_steps(be, plan, shape, L, [d[k] for k in ("inputs", "case_params", "mask", "label")], layout, flat, grad, m, v, preds, sums,
+                      coef, ws, F.WHICH[which], flags, steps)
         be.sync()
         return {"preds": be.host(preds), "sums": be.host(sums), "grad": be.host(grad), "params": be.host(flat)}
     finally:

@@ -11,6 +11,7 @@ import numpy as np
 from cfdbench_amd._capi import CfdError, FnoShape
 from oracle import fno_oracle as O
 from oracle import synth
+from tests import fno_checks as F
 from tests import kernel_checks as K
 
 f64 = np.float64
@@ -19,41 +20,12 @@ nm = K.nm
 WHICH = {"mse": 0, "nmse": 1, "mae": 2}
 
 
-def run_fno(be, params, batch, L, C, H, W, p, m1, m2, which="nmse"):
-    """K.run_fno at modes (m1, m2): forward, loss and backward through cfd_fno_forward / cfd_fno_backward, and the inference-workspace
-    forward; host arrays."""
-    api, P = be.api, be.ptr
-    B = batch["inputs"].shape[0]
-    plan = api.plan_create(H, W, m1, m2)
-    try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
-        pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
-        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        preds, sums, coef, scores = be.out((B, 2, H, W)), be.out((4,)), be.out((2,)), be.out((4,))
-        sh, pr, gr = ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs)
-        api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(ws), 1, be.stream)
-        api.call("cfd_loss_coef", P(sums), P(coef), WHICH[which], 1.0, be.stream)
-        api.call("cfd_fno_backward", plan, sh, pr, gr, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(ws), be.stream)
-        api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
-        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 0))
-        preds0 = be.out((B, 2, H, W))
-        api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), None, P(preds0), None, P(ws0), 0, be.stream)
-        be.sync()
-        return {"preds": be.host(preds), "preds_infer": be.host(preds0), "scores": be.host(scores),
-                "grads": {k: be.host(v) for k, v in gd.items()}}
-    finally:
-        api.plan_destroy(plan)
-
-
 def check_fno_vs_oracle(be, B, C, L, H, W, m1, m2, p=5, border=True, gain=4.0, pseed=7, bseed=8):
     """Whole model at modes (m1, m2) against the fp64 oracle: predictions (training and inference workspaces), the nMSE loss and every
     parameter gradient."""
     params = synth.make_fno_params(pseed, C, L, m1, m2, p, spectral_gain=gain)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=border)
-    out = run_fno(be, params, batch, L, C, H, W, p, m1, m2)
+    out = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2)
     p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
     b64 = {k: v.astype(f64) for k, v in batch.items()}
     ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
@@ -69,57 +41,18 @@ def check_train_step_deferred(be, B, C, L, H, W, m1, m2, p=5, which="mse", flags
     """The fused training step (cfd_fno_forward_train_f / cfd_fno_backward_phase_f / cfd_fno_adam_step) at modes (m1, m2) with the
     CFD_TRAIN_DEFER_* flags `flags` against flags = 0: the many-modes route has no fused kernel to carry a deferred launch, so the two are
     bitwise equal; the first step's gradient against the oracle."""
-    api, P = be.api, be.ptr
     params = synth.make_fno_params(pseed, C, L, m1, m2, p, spectral_gain=4.0)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=True)
-    names = ["fc0.weight", "fc0.bias"] + [f"blocks.{l}.{t}" for l in range(L) for t in ("conv0.weights1", "conv0.weights2", "w0.weight",
-                                                                                        "w0.bias")] + ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-    layout, off = {}, 0
-    for k in names:
-        n = params[k].size * (2 if np.iscomplexobj(params[k]) else 1)
-        layout[k] = (off, n)
-        off += (n + 3) // 4 * 4
-    flat0 = np.zeros(off, np.float32)
-    for k in names:
-        v = params[k]
-        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
-    plan = api.plan_create(H, W, m1, m2)
-    try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
-        sh = ctypes.byref(shape)
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        out = {}
-        for fl in (0, flags):
-            # cfdbench_amd.h, cfd_adam_flat: "exp_avg / exp_avg_sq are the optimizer's state ... the caller zeroes them before step 1"
-            flat, grad, m, v = be.dev(flat0), K.flat_grad_buffer(be, layout, off), be.zeros((off,)), be.zeros((off,))
-            ps, gs = ctypes.byref(K._flat_struct(be, flat, layout, L)), ctypes.byref(K._flat_struct(be, grad, layout, L))
-            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
-            preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
-            for step in range(1, steps + 1):
-                api.call("cfd_fno_forward_train_f", plan, sh, ps, gs, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(coef), P(ws),
-                         WHICH[which], 1.0, 0, fl, be.stream)
-                for phase in range(1, L + 2):
-                    api.call("cfd_fno_backward_phase_f", plan, sh, ps, gs, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(sums),
-                             P(ws), phase, WHICH[which], 0, fl, be.stream)
-                api.call("cfd_fno_adam_step", plan, sh, ps, gs, P(di), P(dc), P(dm), P(sums), P(ws), P(flat), P(grad), P(m), P(v), off,
-                         1e-3, 0.9, 0.999, 1e-8, 0.0, step, 1.0, WHICH[which], 0, fl, be.stream)
-                be.sync()
-                if step == 1:
-                    out[fl] = dict(g1=be.host(grad).copy(), sums1=be.host(sums).copy(), preds1=be.host(preds).copy())
-            out[fl]["flat"] = be.host(flat).copy()
-        a, b = out[0], out[flags]
-        res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
-        p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
-        b64 = {k: v.astype(f64) for k, v in batch.items()}
-        ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
-        rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
-        for k in names:
-            want = rg[k]
-            want = (np.stack([want.real, want.imag], -1) if np.iscomplexobj(want) else want).reshape(-1)
-            res["oracle:" + k] = nm(b["g1"][layout[k][0]:layout[k][0] + layout[k][1]], want)
-        return res
-    finally:
-        api.plan_destroy(plan)
+    out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, m1, m2, which=which, flags=flags, steps=steps)
+    a, b = out[0], out[flags]
+    res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
+    p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
+    b64 = {k: v.astype(f64) for k, v in batch.items()}
+    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
+    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
+    for k in layout:
+        res["oracle:" + k] = nm(F.flat_slice(b["g1"], layout, k), F.flat_view(rg[k]))
+    return res
 
 
 def check_spectral_golden(be, g):
@@ -176,7 +109,7 @@ def check_refusals(be, C=8, B=1, H=64, W=64, m1=16, m2=16, L=1, p=5):
         shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
         gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
+        ps, gs = F.make_param_struct(be, pd, L), F.make_param_struct(be, gd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
         ws = be.scratch(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
         preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))

@@ -15,6 +15,7 @@ import numpy as np
 from cfdbench_amd._capi import CfdError, FnoShape
 from oracle import fno_oracle as O
 from tests import chan_checks as CK
+from tests import fno_checks as F
 from tests import kernel_checks as K
 from tests.backends import POISON_WORD
 
@@ -129,51 +130,6 @@ def _shape(B, H, W, cin, cout, p, C, L, m1, m2, pad):
     return FnoShape(B, H, W, cin, cout, p, C, L, m1, m2, 128, pad)
 
 
-def run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad, which="nmse", infer=True, ws_fill=None, repeat=1):
-    """cfd_fno_forward(training = 1) + cfd_loss_coef + cfd_fno_backward on a shape with `pad` (the plan is the padded grid's), and the
-    inference-workspace forward; host arrays.  `repeat` > 1 runs forward + backward again on the SAME workspace and outputs, untouched in
-    between, and returns one result per run; `ws_fill`: a finite constant the workspaces hold on entry instead of the NaN poison."""
-    api, P = be.api, be.ptr
-    B, cin = batch["inputs"].shape[:2]
-    cout = batch["label"].shape[1]
-    plan = api.plan_create(H + pad, W + pad, m1, m2)
-    try:
-        shape = _shape(B, H, W, cin, cout, p, C, L, m1, m2, pad)
-        pd = {k: be.dev(v) for k, v in params.items()}
-        gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
-        sh, pr, gr = ctypes.byref(shape), ctypes.byref(ps), ctypes.byref(gs)
-
-        def workspace(training):
-            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, training))
-            if ws_fill is not None:
-                words = ws[:ws.shape[0] // 4 * 4].view(np.float32 if be.name == "emul" else be.torch.float32)
-                words[...] = ws_fill
-            return ws
-
-        ws = workspace(1)
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        preds, sums, coef, scores = be.out((B, cout, H, W)), be.out((4,)), be.out((2,)), be.out((4,))
-        runs = []
-        for _ in range(repeat):
-            api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(ws), 1, be.stream)
-            api.call("cfd_loss_coef", P(sums), P(coef), WHICH[which], 1.0, be.stream)
-            api.call("cfd_fno_backward", plan, sh, pr, gr, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(ws), be.stream)
-            api.call("cfd_loss_scores", P(sums), P(scores), be.stream)
-            be.sync()
-            runs.append({"preds": be.host(preds).copy(), "scores": be.host(scores).copy(),
-                         "grads": {k: be.host(v).copy() for k, v in gd.items()}})
-        if infer:
-            ws0 = workspace(0)
-            preds0 = be.out((B, cout, H, W))
-            api.call("cfd_fno_forward", plan, sh, pr, P(di), P(dc), P(dm), None, P(preds0), None, P(ws0), 0, be.stream)
-            be.sync()
-            runs[0]["preds_infer"] = be.host(preds0)
-        return runs if repeat > 1 else runs[0]
-    finally:
-        api.plan_destroy(plan)
-
-
 _CASES, _REFS = {}, {}
 
 
@@ -198,7 +154,7 @@ def check_fno_pad_vs_oracle(be, B, C, L, H, W, pad, m1, m2, p=5, cin=2, cout=2, 
     parameter gradient."""
     key = (B, C, L, H, W, pad, m1, m2, p, cin, cout, gain, pseed, bseed)
     params, batch = _case(*key)
-    out = run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad)
+    out = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad)
     ref, rg = _reference(key)
     res = {"preds": nm(out["preds"], ref["preds"]), "preds_infer": nm(out["preds_infer"], ref["preds"])}
     res["nmse_loss"] = abs(out["scores"][3] - ref["loss"]["nmse"]) / ref["loss"]["nmse"]
@@ -222,53 +178,15 @@ def check_pad_train_step(be, B, C, L, H, W, pad, m1, m2, p=5, cin=2, cout=2, whi
     """The fused training step (cfd_fno_forward_train_f, phases 1 .. L + 1, cfd_fno_adam_step) on a padded shape with the CFD_TRAIN_DEFER_*
     flags `flags` against flags = 0: a padded shape ignores them, so the two are bitwise equal ("bitwise" == 0.0); the first step's flat
     gradient against the padded oracle."""
-    api, P = be.api, be.ptr
     key = (B, C, L, H, W, pad, m1, m2, p, cin, cout, 4.0, pseed, bseed)
     params, batch = _case(*key)
-    names = ["fc0.weight", "fc0.bias"] + [f"blocks.{l}.{t}" for l in range(L) for t in ("conv0.weights1", "conv0.weights2", "w0.weight",
-                                                                                        "w0.bias")] + ["fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
-    layout, off = {}, 0
-    for k in names:
-        n = params[k].size * (2 if np.iscomplexobj(params[k]) else 1)
-        layout[k] = (off, n)
-        off += (n + 3) // 4 * 4
-    flat0 = np.zeros(off, np.float32)
-    for k in names:
-        v = params[k]
-        flat0[layout[k][0]:layout[k][0] + layout[k][1]] = (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).reshape(-1)
-    plan = api.plan_create(H + pad, W + pad, m1, m2)
-    try:
-        shape = _shape(B, H, W, cin, cout, p, C, L, m1, m2, pad)
-        sh = ctypes.byref(shape)
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        out = {}
-        for fl in (0, flags):
-            flat, grad, m, v = be.dev(flat0), K.flat_grad_buffer(be, layout, off), be.zeros((off,)), be.zeros((off,))
-            ps, gs = ctypes.byref(K._flat_struct(be, flat, layout, L)), ctypes.byref(K._flat_struct(be, grad, layout, L))
-            ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, sh, 1))
-            preds, sums, coef = be.out((B, cout, H, W)), be.out((4,)), be.out((2,))
-            for step in range(1, steps + 1):
-                api.call("cfd_fno_forward_train_f", plan, sh, ps, gs, P(di), P(dc), P(dm), P(dl), P(preds), P(sums), P(coef), P(ws),
-                         WHICH[which], 1.0, 0, fl, be.stream)
-                for phase in range(1, L + 2):
-                    api.call("cfd_fno_backward_phase_f", plan, sh, ps, gs, P(di), P(dc), P(dm), P(dl), P(preds), None, P(coef), P(sums),
-                             P(ws), phase, WHICH[which], 0, fl, be.stream)
-                api.call("cfd_fno_adam_step", plan, sh, ps, gs, P(di), P(dc), P(dm), P(sums), P(ws), P(flat), P(grad), P(m), P(v), off,
-                         1e-3, 0.9, 0.999, 1e-8, 0.0, step, 1.0, WHICH[which], 0, fl, be.stream)
-                be.sync()
-                if step == 1:
-                    out[fl] = dict(g1=be.host(grad).copy(), sums1=be.host(sums).copy(), preds1=be.host(preds).copy())
-            out[fl]["flat"] = be.host(flat).copy()
-        a, b = out[0], out[flags]
-        res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
-        _ref, rg = _reference(key, which)
-        for k in names:
-            want = rg[k]
-            want = (np.stack([want.real, want.imag], -1) if np.iscomplexobj(want) else want).reshape(-1)
-            res["oracle:" + k] = nm(b["g1"][layout[k][0]:layout[k][0] + layout[k][1]], want)
-        return res
-    finally:
-        api.plan_destroy(plan)
+    out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, m1, m2, pad, which=which, flags=flags, steps=steps)
+    a, b = out[0], out[flags]
+    res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
+    _ref, rg = _reference(key, which)
+    for k in layout:
+        res["oracle:" + k] = nm(F.flat_slice(b["g1"], layout, k), F.flat_view(rg[k]))
+    return res
 
 
 def _diff(a, b):
@@ -282,8 +200,8 @@ def check_pad_dirty(be, B, C, L, H, W, pad, m1, m2, p=5, pseed=7, bseed=8):
     run whose workspace held a large finite constant bitwise the same again -- a band that is assumed instead of written shows in either."""
     key = (B, C, L, H, W, pad, m1, m2, p, 2, 2, 4.0, pseed, bseed)
     params, batch = _case(*key)
-    first, second = run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad, infer=False, repeat=2)
-    third = run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad, infer=False, ws_fill=3.0e30)
+    first, second = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad, infer=False, repeat=2)
+    third = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad, infer=False, ws_fill=3.0e30)
     ref, _rg = _reference(key)
     return {"second_run": _diff(first, second), "finite_fill": _diff(first, third), "preds": nm(first["preds"], ref["preds"])}
 
@@ -304,10 +222,10 @@ def check_pad_zero_spectral(be, B, C, L, H, W, pad, m1, m2, p=5, pseed=7, bseed=
     params, batch = _case(B, C, L, H, W, pad, m1, m2, p, 2, 2, 4.0, pseed, bseed)
     params = {k: (np.zeros_like(v) if "conv0.weights" in k else v) for k, v in params.items()}
     # the unpadded plan takes the modes its own grid admits: the weights are zero, only their shape is read
-    padded = run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad)
+    padded = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2, pad)
     um1, um2 = min(m1, H // 2), min(m2, W // 2 + 1)
     uparams = {k: (np.zeros(v.shape[:2] + (um1, um2), v.dtype) if "conv0.weights" in k else v) for k, v in params.items()}
-    plain = run_fno(be, uparams, batch, L, C, H, W, p, um1, um2, 0)
+    plain = F.run_fno(be, uparams, batch, L, C, H, W, p, um1, um2, 0)
     return {"preds": nm(padded["preds"], plain["preds"]), "preds_infer": nm(padded["preds_infer"], plain["preds_infer"])}
 
 
@@ -339,7 +257,7 @@ def check_pad_refusals(be, C=6, L=1, p=5):
             sh = ctypes.byref(shape)
             pd = {k: be.dev(v) for k, v in params.items()}
             gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-            pr, gr = ctypes.byref(K.make_param_struct(be, pd, L)), ctypes.byref(K.make_param_struct(be, gd, L))
+            pr, gr = ctypes.byref(F.make_param_struct(be, pd, L)), ctypes.byref(F.make_param_struct(be, gd, L))
             di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
             ws = be.scratch(1 << 20)
             preds, sums, coef = be.out(batch["label"].shape), be.out((4,)), be.out((2,))
@@ -382,7 +300,7 @@ def check_pad_zero_is_unpadded(be, B=1, C=6, L=2, H=16, W=20, m1=4, m2=5, p=5):
     """pad = 0 with an unpadded plan runs and is bitwise the same call through an 11-field FnoShape; cfd_fno_workspace_bytes agrees too."""
     api = be.api
     params, batch = _case(B, C, L, H, W, 0, m1, m2, p, 2, 2, 4.0, 57, 58)
-    a = run_fno(be, params, batch, L, C, H, W, p, m1, m2, 0)
+    a = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2, 0)
     out = {}
     plan = api.plan_create(H, W, m1, m2)
     try:
@@ -392,7 +310,6 @@ def check_pad_zero_is_unpadded(be, B=1, C=6, L=2, H=16, W=20, m1=4, m2=5, p=5):
                                      api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(s12), t) > 0 for t in (0, 1))
     finally:
         api.plan_destroy(plan)
-    from tests import modes_checks as MK
-    b = MK.run_fno(be, params, batch, L, C, H, W, p, m1, m2)
+    b = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2)  # (no pad argument: the route a caller of the 11-field shape takes)
     out["bitwise"] = K.nan_max(_diff(a, b), np.max(np.abs(a["preds_infer"] - b["preds_infer"]))) == 0.0
     return out

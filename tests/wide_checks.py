@@ -10,6 +10,7 @@ import numpy as np
 from cfdbench_amd._capi import CfdError, FnoShape
 from oracle import fno_oracle as O
 from oracle import synth
+from tests import fno_checks as F
 from tests import kernel_checks as K
 
 f64 = np.float64
@@ -105,38 +106,10 @@ def check_head_fwd(be, B, C, HW, act, Co=2, border=True, seed=4):
     return res
 
 
-def run_fno_forward(be, params, batch, L, C, H, W, p, act_dtype=0):
-    """cfd_fno_forward_ex with the loss sums (training = 1 workspace) and without (inference workspace); host arrays."""
-    api, P = be.api, be.ptr
-    B = batch["inputs"].shape[0]
-    plan = api.plan_create(H, W, 12, 12)
-    try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
-        pd = {k: be.dev(v) for k, v in params.items()}
-        ps = K.make_param_struct(be, pd, L)
-        di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
-        out = {}
-        ws = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 1))
-        preds, sums = be.out((B, 2, H, W)), be.out((4,))
-        api.call("cfd_fno_forward_ex", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), P(dl), P(preds), P(sums),
-                 P(ws), 1, act_dtype, be.stream)
-        be.sync()
-        out["preds"], out["sums"] = be.host(preds), be.host(sums)
-        ws0 = be.scratch(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), 0))
-        preds0 = be.out((B, 2, H, W))
-        api.call("cfd_fno_forward_ex", plan, ctypes.byref(shape), ctypes.byref(ps), P(di), P(dc), P(dm), None, P(preds0), None,
-                 P(ws0), 0, act_dtype, be.stream)
-        be.sync()
-        out["preds_infer"] = be.host(preds0)
-        return out
-    finally:
-        api.plan_destroy(plan)
-
-
 def check_fno_forward_vs_oracle(be, B, C, L, H, W, p=5, border=False, gain=4.0, pseed=7, bseed=8):
     params = synth.make_fno_params(pseed, C, L, 12, 12, p, spectral_gain=gain)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=border)
-    out = run_fno_forward(be, params, batch, L, C, H, W, p)
+    out = F.run_fno(be, params, batch, L, C, H, W, p, backward=False)  # (the wide route's backward: K.check_fno_vs_oracle)
     p64 = {k: v.astype(np.complex128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
     b64 = {k: v.astype(f64) for k, v in batch.items()}
     ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
@@ -166,7 +139,7 @@ def check_wide_refusals(be, C=64, B=1, H=64, W=64, L=1, p=5):
         shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
         gd = {k: be.out(v.shape, np.complex64 if np.iscomplexobj(v) else np.float32) for k, v in params.items()}
-        ps, gs = K.make_param_struct(be, pd, L), K.make_param_struct(be, gd, L)
+        ps, gs = F.make_param_struct(be, pd, L), F.make_param_struct(be, gd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))
         ws = be.scratch(api.size("cfd_fno_workspace_bytes_ex", plan, ctypes.byref(shape), 1, 0))
         preds, sums, coef = be.out((B, 2, H, W)), be.out((4,)), be.out((2,))
