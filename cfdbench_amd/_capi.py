@@ -28,6 +28,8 @@ class FnoParams(C.Structure):
         ("spec_w1", C.c_void_p * CFD_MAX_LAYERS), ("spec_w2", C.c_void_p * CFD_MAX_LAYERS),
         ("w0_w", C.c_void_p * CFD_MAX_LAYERS), ("w0_b", C.c_void_p * CFD_MAX_LAYERS),
         ("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p),
+        # ABI 603, read from the `grads` struct only; NULL = not asked (include/cfdbench_amd.h)
+        ("d_inputs", C.c_void_p), ("d_case_params", C.c_void_p),
     ]
 
 
@@ -40,7 +42,7 @@ class FfnStackArgs(C.Structure):
 
 
 _P = C.c_void_p
-ABI_VERSION = 602  # include/cfdbench_amd.h: CFD_ABI_VERSION
+ABI_VERSION = 603  # include/cfdbench_amd.h: CFD_ABI_VERSION
 _I = C.c_int
 _F = C.c_float
 _Z = C.c_size_t

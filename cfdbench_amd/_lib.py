@@ -76,17 +76,19 @@ class FnoCall(NamedTuple):
     defers: bool  # the route honours CFD_TRAIN_DEFER_*
 
 
-def fno_call(cfg: dict, B: int, in_chan: int, H: int, W: int, n_case_params: int, device) -> FnoCall:
+def fno_call(cfg: dict, B: int, in_chan: int, H: int, W: int, n_case_params: int, device, input_grads: bool = False) -> FnoCall:
     """What a whole-model C call needs besides its tensors, from ``Fno2d.abi_config()`` and one batch's extents: the plan and the
     ``FnoShape``.  The one place that knows the domain-padding rule: ``Fno2d(padding=)`` runs its FnoBlocks on (H + pad, W + pad), so
     that is the grid the plan is for, while the shape carries the data grid and ``pad``.
 
     ``defers`` mirrors ``route()`` of csrc/fno.cpp (the table above it): the wide route (hidden > 32), the many-modes route (modes1 > 15
     or modes2 > 16, or a plan wider than 80 columns: cfd_plan_create), the head's channel route (out_chan > 2) and a padded shape have
-    none of the kernels that carry a deferred job and ignore the flags, so their gradients are final after the pass.  Only
-    ``FnoTrainEngine.gradients()`` reads it."""
+    none of the kernels that carry a deferred job and ignore the flags, so their gradients are final after the pass; the same holds for
+    a pass whose ``grads`` struct asks for the gradients of the inputs or case parameters (``input_grads``; ABI 603).  Only
+    ``FnoTrainEngine.gradients()`` reads ``defers``, and no caller sets ``input_grads`` yet: the engine never asks for input gradients
+    and ``FnoForwardFn`` passes no flags.  The argument keeps this mirror of ``route()`` complete for the caller that will."""
     pad = int(cfg.get("padding", 0))
     m1, m2 = cfg["modes1"], cfg["modes2"]
     shape = FnoShape(B, H, W, in_chan, cfg["out_chan"], n_case_params, cfg["hidden"], cfg["num_layers"], m1, m2, cfg["head"], pad)
-    defers = cfg["hidden"] <= 32 and m1 <= 15 and m2 <= 16 and W + pad <= 80 and cfg["out_chan"] <= 2 and pad == 0
+    defers = cfg["hidden"] <= 32 and m1 <= 15 and m2 <= 16 and W + pad <= 80 and cfg["out_chan"] <= 2 and pad == 0 and not input_grads
     return FnoCall(plan(H + pad, W + pad, m1, m2, device.index), shape, defers)

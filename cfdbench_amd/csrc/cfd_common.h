@@ -176,6 +176,15 @@ int cfd_int_stem_pad(const float* inputs, const float* mask, const float* case_p
 int cfd_int_pad_crop(const float* in, float* out, long n, int H, int W, int pad, void* stream);   // (n, H+pad, W+pad) -> (n, H, W)
 int cfd_int_pad_embed(const float* in, float* out, long n, int H, int W, int pad, void* stream);  // (n, H, W) -> (n, H+pad, W+pad), zero band
 
+// Gradients with respect to the model's inputs and case parameters (ingrad.hip; cfd_fno_params.d_inputs / d_case_params of the grads
+// struct): one pass over g0 = d loss / d fc0 output (B, C, HW) on the DATA grid, fp32, with fc0.weight w (C, in_chan + 3 + P).
+//   d_inputs[b, i, px]  = sum_c w[c, i] g0[b, c, px]                      (B, in_chan, HW); NULL = not asked
+//   d_case_params[b, k] = sum_c w[c, in_chan + 3 + k] sum_px g0[b, c, px]  (B, P); NULL or P == 0 = not asked
+// ws: ws_bytes of 16-byte aligned scratch for the partial records of d_case_params (summed in a fixed order by a second launch); the
+// launcher cuts as many records per batch entry as fit.  C <= CFD_WIDE_MAX, in_chan + 3 + P <= 32, B C HW < 2^31.
+int cfd_int_fno_ingrad(const float* g0, const float* w, float* d_inputs, float* d_case_params, void* ws, size_t ws_bytes, int B, int in_chan,
+                       int P, int C, int HW, void* stream);
+
 // Wide-channel route (wide.hip): layers with more than 32 input or output channels, up to CFD_WIDE_MAX, fp32 storage.
 #define CFD_WIDE_MAX 128
 int cfd_int_wide_mix(const cfd_plan* p, const float* xh, const float* w1, const float* w2, float* z, int B, int Cin, int Cout,

@@ -153,6 +153,8 @@ struct View {
 //   pad > 0                    no                       no                       no               no                         no
 //   bf16 storage               no                       no                       as narrow        no                         no
 //   num_layers == 0            no                       no                       as narrow        no                         no
+//   grads->d_inputs or         as narrow                no                       no               no                         no
+//     grads->d_case_params
 //   narrow                     cfd_int_dft_stem_ok      cfd_int_stemg_ok         flag, which = 1  flag, block_bwd_fused      flag, stemg
 //
 // stem_in_dft: the lifting layer rides in the first forward transform (round 6: on 64 x 64 one launch and one activation-sized read less).
@@ -163,18 +165,24 @@ struct View {
 // scale / head / stem: the CFD_TRAIN_DEFER_* bits of `flags` that apply.  The wide route, the many-modes route and the head's channel route
 //   have none of the fused kernels that carry a deferred job, and a padded shape's lifting layer and head are kernels of their own (pad.hip):
 //   every flag is ignored there.  scale is the only one that bf16 storage keeps; stem implies stemg.
+// grads->d_inputs / d_case_params (ABI 603): the input gradients are taken from g_0 in memory (ingrad.hip), so the block kernel must store
+//   it (no stemg, hence no stem), and they are final after the pass: a deferred normaliser would leave them short of its factor, and the
+//   head's deferral goes with it so that the route is the unfused one as a whole.  The forward trunk is untouched.
 struct Route {
     bool stem_in_dft, stemg;
     bool scale, head, stem;
 };
-Route route(const cfd_plan* p, const cfd_fno_shape* s, const View& v, int which, int dt, int flags, const void* inputs, const void* mask) {
+bool wants_ingrad(const cfd_fno_params* g) { return g && (g->d_inputs || g->d_case_params); }
+Route route(const cfd_plan* p, const cfd_fno_shape* s, const View& v, int which, int dt, int flags, const void* inputs, const void* mask,
+            const cfd_fno_params* grads) {
     const int B = s->B, C = s->hidden, NL = s->num_layers;
     const bool fusable = s->pad == 0 && dt == CFD_DT_F32 && NL >= 1;
-    const bool defers = !(C > 32 || p->many || s->out_chan > 2 || s->pad > 0);
+    const bool ingrad = wants_ingrad(grads);
+    const bool defers = !(C > 32 || p->many || s->out_chan > 2 || s->pad > 0 || ingrad);
     Route r{};
     r.stem_in_dft = fusable && cfd_int_dft_stem_ok(p, B, s->in_chan, s->n_case_params, C, inputs, mask, v.act(0));
     if (!v.training) return r;  // (inference has no gradient and defers nothing)
-    r.stemg = fusable && cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, v.z());
+    r.stemg = fusable && !ingrad && cfd_int_stemg_ok(p, B, C, s->in_chan, s->n_case_params, inputs, mask, v.z());
     r.scale = defers && (flags & CFD_TRAIN_DEFER_SCALE) && which == 1;
     // backward phase 1 = FnoBlock NL-1: gcur = gA, gnext = gB, aprev = a_{NL-1} when NL > 1
     r.head = defers && fusable && (flags & CFD_TRAIN_DEFER_HEAD) && cfd_int_block_bwd_fused(p, B, C, v.gA(), v.gB(), NL > 1 ? v.act(NL - 1) : nullptr, v.z());
@@ -250,7 +258,7 @@ extern "C" int cfd_fno_forward_ex(const cfd_plan* p, const cfd_fno_shape* s, con
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || !training, CFD_ERR_UNSUPPORTED, "cfd_fno_forward: bf16 activation storage is an inference path (training = 0)");
     const int dt = act_dtype;
     const View v(p, s, training, dt, ws);
-    const Route rt = route(p, s, v, 0, dt, 0, inputs, mask);  // (flags = 0: this call defers nothing; the trunk reads stem_in_dft)
+    const Route rt = route(p, s, v, 0, dt, 0, inputs, mask, nullptr);  // (flags = 0: this call defers nothing; the trunk reads stem_in_dft)
     CFD_TRY(trunk(p, s, prm, v, rt, dt, inputs, case_params, mask, stream));
     const void* aL;
     CFD_TRY(head_input(s, v, stream, &aL));
@@ -294,7 +302,9 @@ extern "C" int cfd_fno_forward_train_f(const cfd_plan* p, const cfd_fno_shape* s
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_forward_train: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     const int dt = act_dtype;
     const View v(p, s, 1, dt, ws);
-    const Route rt = route(p, s, v, which, dt, flags, inputs, mask);
+    CFD_REQUIRE(dt == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
+                "cfd_fno_forward_train: grads->d_inputs / d_case_params need fp32 activation storage");
+    const Route rt = route(p, s, v, which, dt, flags, inputs, mask, g);
     const int B = s->B, C = s->hidden, HW = s->H * s->W, NL = s->num_layers, pad = s->pad;  // HW: the data grid
     // the label's energy and the gradient coefficients: independent of the network (scratch is free until the head); with
     // side_stream bit 1 they run beside the lifting layer on the side stream and join in front of the head (off by default:
@@ -354,6 +364,8 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     CFD_REQUIRE(prm && g && inputs && ws, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: act_dtype %d (0 = fp32, 1 = bf16)", act_dtype);
     const int dt = act_dtype;
+    CFD_REQUIRE(dt == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
+                "cfd_fno_backward_phase: grads->d_inputs / d_case_params need fp32 activation storage");
     const View v(p, s, 1, dt, ws);
     const int B = s->B, C = s->hidden, HW = s->H * s->W, HWp = p->H * p->W, NL = s->num_layers, pad = s->pad;  // HW: data grid, HWp: the plan's
     CFD_REQUIRE(phase >= 0 && phase <= NL + 1, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: phase %d outside 0..%d", phase, NL + 1);
@@ -369,7 +381,7 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
     const int done = phase - 1;  // blocks already processed: the gradient sits in gA after an even count
     float* gcur = (done & 1) ? v.gB() : v.gA();
     float* gnext = (done & 1) ? v.gA() : v.gB();
-    const Route rt = route(p, s, v, which, dt, flags, inputs, mask);
+    const Route rt = route(p, s, v, which, dt, flags, inputs, mask, g);
     CFD_REQUIRE(!rt.head || sums, CFD_ERR_INVALID_ARG, "cfd_fno_backward_phase: CFD_TRAIN_DEFER_HEAD needs the `sums` of the forward call");
     if (phase == NL + 1) {
         if (rt.stem) return CFD_OK;  // cfd_fno_adam_step's launch finishes the lifting layer's gradient
@@ -381,7 +393,13 @@ extern "C" int cfd_fno_backward_phase_f(const cfd_plan* p, const cfd_fno_shape* 
             g0 = gnext;
         }
         const cfd_plan dp = data_plan(p, s, v.coord());
-        return cfd_fno_stem_bwd(&dp, g0, inputs, mask, case_params, g->fc0_w, g->fc0_b, v.scratch(), B, s->in_chan, s->n_case_params, C, stream);
+        CFD_TRY(cfd_fno_stem_bwd(&dp, g0, inputs, mask, case_params, g->fc0_w, g->fc0_b, v.scratch(), B, s->in_chan, s->n_case_params, C, stream));
+        if (!wants_ingrad(g)) return CFD_OK;
+        // d loss / d inputs, d loss / d case_params from the same g_0 (the cropped one with domain padding); its partial records go where the
+        // lifting layer's weight gradient has just finished with its own (same stream), so the workspace does not grow
+        return cfd_int_fno_ingrad(g0, prm->fc0_w, g->d_inputs, g->d_case_params, v.scratch(),
+                                  cfd_fno_stem_bwd_workspace_bytes(&dp, B, s->in_chan, s->n_case_params, C), B, s->in_chan, s->n_case_params, C,
+                                  HW, stream);
     }
     const int l = NL - phase;
     const int act = l > 0;
@@ -438,7 +456,9 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
     const View v(p, s, 1, act_dtype, ws);
-    const Route rt = route(p, s, v, which, act_dtype, flags, inputs, mask);
+    CFD_REQUIRE(act_dtype == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
+                "cfd_fno_adam_step: grads->d_inputs / d_case_params need fp32 activation storage");
+    const Route rt = route(p, s, v, which, act_dtype, flags, inputs, mask, g);
     CFD_REQUIRE(!rt.scale || sums, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_TRAIN_DEFER_SCALE needs the `sums` of the forward call");
     StemAdamJob job{};
     if (rt.stem) {

@@ -303,8 +303,10 @@ def scores_from_sums(sums: Tensor, normalize: bool) -> dict:
 FNO_PARAM_ORDER_DOC = "fc0.weight, fc0.bias, [weights1, weights2, w0.weight, w0.bias] * L, fc1.weight, fc1.bias, fc2.weight, fc2.bias"
 
 
-def _param_struct(ptrs: Sequence[Optional[int]], L: int) -> FnoParams:
+def _param_struct(ptrs: Sequence[Optional[int]], L: int, d_inputs: Optional[int] = None, d_case_params: Optional[int] = None) -> FnoParams:
+    """``d_inputs`` / ``d_case_params``: the two fields of ABI 603, read from a ``grads`` struct only (None = not asked)."""
     s = FnoParams()
+    s.d_inputs, s.d_case_params = d_inputs, d_case_params
     s.fc0_w, s.fc0_b = ptrs[0], ptrs[1]
     for l in range(L):
         s.spec_w1[l], s.spec_w2[l], s.w0_w[l], s.w0_b[l] = ptrs[2 + 4 * l: 6 + 4 * l]
@@ -313,7 +315,10 @@ def _param_struct(ptrs: Sequence[Optional[int]], L: int) -> FnoParams:
 
 
 class FnoForwardFn(torch.autograd.Function):
-    """(preds, sums) = Fno2d(inputs, case_params, mask, label); params in FNO_PARAM_ORDER_DOC order."""
+    """(preds, sums) = Fno2d(inputs, case_params, mask, label); params in FNO_PARAM_ORDER_DOC order.
+
+    Differentiable in the parameters, in ``inputs`` and in ``case_params`` (the lifting layer's adjoint, csrc/ingrad.hip: what a rollout
+    differentiated through its fed-back frames needs); ``mask`` and ``label`` get no gradient."""
 
     @staticmethod
     def forward(ctx, cfg: dict, inputs: Tensor, case_params: Tensor, mask: Optional[Tensor], label: Optional[Tensor],
@@ -321,6 +326,7 @@ class FnoForwardFn(torch.autograd.Function):
         _require_cuda(inputs, case_params, mask, label, *params)
         api = _lib.api()
         L = cfg["num_layers"]
+        ctx.arg_dtypes = (inputs.dtype, case_params.dtype)  # (the gradients go back in the arguments' own types)
         inputs, case_params, mask, label = _f32c(inputs), _f32c(case_params), _f32c(mask), _f32c(label)
         B, in_chan, H, W = inputs.shape
         out_chan = cfg["out_chan"]
@@ -335,7 +341,7 @@ class FnoForwardFn(torch.autograd.Function):
         # needs_input_grad reflects requires_grad whatever the grad mode is (and grad mode is always off inside
         # Function.forward), so the caller passes torch.is_grad_enabled(): under no_grad / inference_mode the forward-only
         # workspace is used and nothing is saved.
-        training = bool(cfg.get("grad_enabled", True)) and any(ctx.needs_input_grad[5:])
+        training = bool(cfg.get("grad_enabled", True)) and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or any(ctx.needs_input_grad[5:]))
         ws = _bytes(api.size("cfd_fno_workspace_bytes", plan, ctypes.byref(shape), int(training)), inputs.device)
         preds = torch.empty((B, out_chan, H, W), dtype=torch.float32, device=inputs.device)
         sums = torch.empty(4, dtype=torch.float32, device=inputs.device) if label is not None else None
@@ -371,16 +377,24 @@ class FnoForwardFn(torch.autograd.Function):
         gext = _f32c(gpreds) if gpreds is not None else None
         if not use_label and gext is None:
             return (None,) * (5 + len(flat))
+        # (frozen parameters with inputs.requires_grad_(): the pass writes every parameter gradient all the same; they are dropped below)
         grads = [torch.empty_like(t) for t in flat]
+        d_inputs = torch.empty_like(inputs) if ctx.needs_input_grad[1] else None
+        d_cp = torch.empty_like(case_params) if ctx.needs_input_grad[2] and case_params.shape[1] > 0 else None
         pstruct = _param_struct([t.data_ptr() for t in flat], L)
-        gstruct = _param_struct([t.data_ptr() for t in grads], L)
+        gstruct = _param_struct([t.data_ptr() for t in grads], L, _ptr(d_inputs), _ptr(d_cp))
         api.call("cfd_fno_backward", ctx.plan, ctypes.byref(ctx.shape), ctypes.byref(pstruct), ctypes.byref(gstruct),
                  _ptr(inputs), _ptr(case_params), _ptr(mask), _ptr(label if use_label else None), _ptr(preds), _ptr(gext),
                  _ptr(coef), _ptr(ctx.ws), _stream())
         ctx.ws = None
-        out = [torch.view_as_complex(g) if (g.dim() == 5 and g.shape[-1] == 2) else g for g in grads]
+        out = [(torch.view_as_complex(g) if (g.dim() == 5 and g.shape[-1] == 2) else g) if need else None
+               for g, need in zip(grads, ctx.needs_input_grad[5:])]
         # reshape 1x1 conv weights back to (out, in, 1, 1): empty_like(flat) already carries the parameter's shape
-        return (None, None, None, None, None, *out)
+        if d_inputs is not None:
+            d_inputs = d_inputs.to(ctx.arg_dtypes[0])
+        if d_cp is not None:
+            d_cp = d_cp.to(ctx.arg_dtypes[1])
+        return (None, d_inputs, d_cp, None, None, *out)
 
 
 # ----------------------------------------------------------------------------------------------------

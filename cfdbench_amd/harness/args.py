@@ -14,7 +14,9 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``graph`` (1: the autograd train step -- forward, loss, backward, Adam -- is captured once as a HIP graph and replayed per batch;
     single process, no gradient accumulation, models without per-step host state, i.e. not the ResNet's dropout),
     ``dtype`` ("bf16": the FNO's activations between kernels are stored as bf16 -- test_multistep: BASELINE configs[4];
-    train_auto --fused 1: bf16-storage training with fp32 master weights, gradients and optimiser).
+    train_auto --fused 1: bf16-storage training with fp32 master weights, gradients and optimiser),
+    ``unroll_steps`` (train_auto, K > 1: the FNO is trained through a K-step rollout -- loss = mean nmse of K steps with every prediction
+    fed back as the next input, cfdbench_amd/unroll.py; eager autograd path only; 1 = the reference's one-step loop).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -44,7 +46,7 @@ _FLAGS: Dict[str, Any] = dict(
     lr_step_size=20, lr_gamma=0.9,
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
-    lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1,
+    lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -100,6 +102,7 @@ def is_args_valid(args: Args) -> None:
     if args.graph:
         assert not args.fused, "--graph 1 captures the autograd step; the fused FNO engine has its own launch path"
         assert args.gradient_accumulation_steps == 1, "--graph 1 captures one optimiser step per batch"
+    assert args.unroll_steps >= 1, "--unroll_steps counts the model steps of one training window (1 = the one-step loop)"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

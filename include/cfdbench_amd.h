@@ -59,7 +59,7 @@ extern "C" {
  * changes (500, round 5: the statistics records of cfd_conv2d_fwd_stats / cfd_batchnorm_fwd_stats are (C, slots, 4) floats since
  * round 4 -- a caller that still allocates (C, slots, 2) must fail at load time, not write out of bounds; the default of the
  * "act_pieces" knob is 3).  The Python binding refuses a library whose version differs (cfdbench_amd/_capi.py). */
-#define CFD_ABI_VERSION 602
+#define CFD_ABI_VERSION 603
 int cfd_version(void);
 const char* cfd_last_error(void);
 
@@ -502,6 +502,15 @@ typedef struct { /* device pointers, reference state_dict order (SURVEY.md 8b "C
     float* fc1_b;
     float* fc2_w;
     float* fc2_b;
+    /* Appended in ABI 603, read ONLY from the `grads` struct of the training forward, the backward phases and cfd_fno_adam_step; NULL = not
+     * asked (a caller that fills a zeroed struct gets the behaviour of ABI 602 bit for bit).  d_inputs (B, in_chan, H, W) receives d loss /
+     * d inputs, d_case_params (B, n_case_params) d loss / d case_params (ignored when n_case_params = 0); each is overwritten by backward
+     * phase num_layers + 1.  Limits: fp32 activation storage only (bf16: CFD_ERR_UNSUPPORTED before any launch); no gradient of the mask;
+     * with either pointer set every CFD_TRAIN_DEFER_* flag and the lifting layer's fused sums are off -- d loss / d fc0 output must reach
+     * memory, and a deferred normaliser would leave these gradients short of its factor -- so the parameter gradients are those of
+     * cfd_tune_set("stem_fuse", 0).  The same `grads` struct goes to the forward call, every phase and cfd_fno_adam_step. */
+    float* d_inputs;
+    float* d_case_params;
 } cfd_fno_params;
 
 /* Bytes of caller-provided workspace: activations kept for backward + scratch.  training=0: forward only.   */
@@ -582,7 +591,10 @@ int cfd_fno_adam_step(const cfd_plan* plan, const cfd_fno_shape* shape, const cf
                       float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
                       float weight_decay, int step, float grad_scale, int which, int act_dtype, int flags, void* stream);
 
-/* grads: same layout as params, every tensor overwritten.  coef/gpreds_ext as in cfd_fno_head_bwd.           */
+/* grads: same layout as params, every tensor overwritten.  coef/gpreds_ext as in cfd_fno_head_bwd.  grads->d_inputs /
+ * grads->d_case_params (cfd_fno_params, ABI 603; NULL = not asked): the gradients with respect to `inputs` and `case_params`, written by
+ * the last phase in one more pass over d loss / d fc0 output, with a fixed summation order (two calls give the same bits) and inside the
+ * workspace the pass already has.  With gpreds_ext = the d_inputs of a later step this chains a rollout's gradient through the ABI. */
 int cfd_fno_backward(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params,
                      const cfd_fno_params* grads, const float* inputs, const float* case_params, const float* mask,
                      const float* label, const float* preds, const float* gpreds_ext, const float* coef, void* ws,
