@@ -2099,6 +2099,19 @@ __device__ __forceinline__ void cfd_strow4(float* p, float4 v) {
     if constexpr (GEN) cfd_st4u(p, v);
     else *reinterpret_cast<float4*>(p) = v;
 }
+// acc[r] = fmaf(w, v[r], acc[r]), r = 0 .. 3, as two v_pk_fma_f32 on the register pairs (0, 1) and (2, 3).  Plain vector code and not
+// inline assembly on purpose: the accumulators are MFMA results, and the wait states between an MFMA's write and a VALU read of the
+// same registers are inserted by the compiler only for instructions it can see.  The weight broadcast is the compiler's (an operand
+// select or one duplicated pair per call); build.py's lint keeps the op_sel:[0,1,..] forms out.
+__device__ __forceinline__ f32x4 cfd_fma4_bcast(f32x4 acc, float w, f32x4 v) {
+    const cfd_f2 ws = {w, w};
+    const cfd_f2 a0 = cfd_fma2(ws, v.xy, acc.xy), a1 = cfd_fma2(ws, v.zw, acc.zw);
+    return __builtin_shufflevector(a0, a1, 0, 1, 2, 3);
+}
+// CFD_BLOCK_MIX: the FMAs of the channel mix -- 1 = scalar v_fmac_f32, 2 = packed v_pk_fma_f32 (same bits; tools/build_variant.sh)
+#ifndef CFD_BLOCK_MIX
+#define CFD_BLOCK_MIX 2
+#endif
 template <int NW, int DPW, int NCH, bool ACT, bool TRANS, bool DGELU, bool TAIL, int AP, bool GEN, bool STEMG = false>
 __global__ __launch_bounds__(64 * NW) void k_block(const float* __restrict__ src, const float* __restrict__ z,
                                                    const float* __restrict__ w, const float* __restrict__ bias,
@@ -2114,7 +2127,7 @@ __global__ __launch_bounds__(64 * NW) void k_block(const float* __restrict__ src
     // the chunk before the next one is committed), the prefetch two chunks ahead in registers stays
     constexpr bool SBUF = NW == 8 && DPW == 4 && NCH == 4;
     constexpr int NBUF = SBUF ? 1 : 2;
-    __shared__ float4 s_src[NBUF * NW * 16 * 16];     // [buf][channel in chunk][row][float4 column]
+    __shared__ float4 s_src[NBUF * NW * 16 * 16];     // [buf][channel in chunk][column j of the lane's four][lane] -> rows 4q .. 4q+3
     __shared__ bf16x8 s_tab3[CFD_B3_TABV];            // split-bf16 inverse tables: ta3 of every tile (T <= 4) | tb3
     __shared__ float s_z[NW * DPW * CFD_KB_ZS];      // kept modes of this wave's destination channels
     if (TAIL && (int)blockIdx.x < tail.nblk) {
@@ -2154,14 +2167,16 @@ __global__ __launch_bounds__(64 * NW) void k_block(const float* __restrict__ src
     const int M2 = 4 * m1 * m2;
     const int G = TPW * NCH;  // chunks of this workgroup's tiles, streamed tile after tile; chunk g lives in buffer g & 1
     auto rowc = [&](int x) { return GEN ? (x < H ? x : H - 1) : x; };  // rows past H: clamped on load (their results are never stored)
-    // ---- this wave's slice of a source chunk: channel ((g % NCH)*NW + wave) of tile g / NCH, rows 4k+q ----
+    // ---- this wave's slice of a source chunk: channel ((g % NCH)*NW + wave) of tile g / NCH, rows 4q+k ----
+    // (lane (q, n) fetches the 4 x 4 block -- rows 4q .. 4q+3, columns 4n .. 4n+3 -- that lane (q, n) of every wave accumulates; one load
+    // instruction still reads whole 256-byte rows)
     float4 R[2][4];
     float RT[2][GEN ? 4 : 1];  // GEN: tail values of row 4n + q (lanes n < 4), chunk parity as R
     auto fetch = [&](int g, float4 (&r)[4], float (&rt)[GEN ? 4 : 1]) {
         const int tl = g / NCH, ch = (g - tl * NCH) * NW + wave, t = t0 + tl;
         const float* pl = src + ((size_t)b * Cs + (ch < Cs ? ch : 0)) * HW;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = cfd_ldrow4<GEN>(pl + (size_t)rowc(16 * t + q + 4 * k) * P + 4 * n);
+        for (int k = 0; k < 4; ++k) r[k] = cfd_ldrow4<GEN>(pl + (size_t)rowc(16 * t + 4 * q + k) * P + 4 * n);
         if constexpr (GEN) {
             const float* pt = pl + (size_t)rowc(16 * t + q + 4 * (n & 3)) * P + W;
 #pragma unroll
@@ -2170,13 +2185,18 @@ __global__ __launch_bounds__(64 * NW) void k_block(const float* __restrict__ src
     };
     auto commit = [&](int c, int buf, const float4 (&r)[4], const float (&rt)[GEN ? 4 : 1]) {
         const bool live = c * NW + wave < Cs;
+        f32x4 blk[4];  // the block's rows; stored transposed (a renaming of registers): one float4 per column j = the rows r = 0 .. 3,
+                       // the operand order of the packed channel mix
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float4 v = r[k];
             if constexpr (ACT) cfd_gelu4(v.x, v.y, v.z, v.w);
             if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            s_src[((buf * NW + wave) * 16 + 4 * k + q) * 16 + n] = v;
+            blk[k] = f32x4{v.x, v.y, v.z, v.w};
         }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            s_src[((buf * NW + wave) * 4 + j) * 64 + lane] = make_float4(blk[0][j], blk[1][j], blk[2][j], blk[3][j]);
         if constexpr (GEN) {
             if (n < 4) {
                 float4 v = make_float4(rt[0], rt[1], rt[2], rt[3]);
@@ -2351,52 +2371,96 @@ __global__ __launch_bounds__(64 * NW) void k_block(const float* __restrict__ src
                     }
                 }
             }
-            // channel mix of this chunk (dead channels hold zeros in LDS and get zero weights); the LDS reads of
-            // source channel sl+1 are issued before the FMAs of channel sl
+            // channel mix of this chunk (dead channels hold zeros in LDS and get zero weights).  A lane reads hh[jj] = rows 4q .. 4q+3 of
+            // column 4n + j, the register order of acc[dd][j]: two v_pk_fma_f32 per (dd, j), the same fmaf per element in the same order
+            // over source channels as a scalar loop (CFD_BLOCK_MIX = 1 builds that one).  The reads run half a channel ahead of the
+            // FMAs -- columns 2, 3 of channel sl are in flight during the FMAs of its columns 0, 1, columns 0, 1 and the weights of
+            // channel sl+1 during those of columns 2, 3 -- which costs no second set of value registers (a whole channel ahead spills:
+            // the (10,2,2) forward lives in 168 registers).  The scheduling fences keep that order (left alone the compiler sinks
+            // every read to its first use); the waits are the counted lgkmcnt the compiler places at the first uses.  Rolled over
+            // PAIRS of channels so that the two weight sets are statically named.
             {
-                float4 v[2][4], wq[2][WS / 4];
-                auto lds_fetch = [&](int sl, float4 (&vv)[4], float4 (&ww)[WS / 4]) {
+                f32x4 h0[2], h1[2], wa[WS / 4], wb[WS / 4];
+                float ta = 0.f, tb = 0.f;
+                // (opaque bases, one per chunk: every read of a pair is base + immediate offset)
+                const float4* sp = s_src + cfd_opaque(lb * NW * 256 + lane);                     // channel sl, column j: sp[(4 * sl + j) * 64]
+                const float4* wp4 = s_w + cfd_opaque((wave * (NW * NCH) + c * NW) * (WS / 4));  // channel sl: wp4[sl * (WS / 4) + h]
+                const float* tp = s_tail + (GEN ? cfd_opaque((lb * NW * 16 + n) * 4 + q) : 0);  // GEN, channel sl: tp[sl * 64]
+                auto rd_half = [&](int sl, int j0, f32x4 (&hh)[2]) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) vv[r] = s_src[((lb * NW + sl) * 16 + 4 * q + r) * 16 + n];
-#pragma unroll
-                    for (int h = 0; h < WS / 4; ++h) ww[h] = s_w[(wave * (NW * NCH) + c * NW + sl) * (WS / 4) + h];
+                    for (int jj = 0; jj < 2; ++jj) {
+                        const float4 x = sp[(4 * sl + j0 + jj) * 64];
+                        hh[jj] = f32x4{x.x, x.y, x.z, x.w};
+                    }
                 };
-                lds_fetch(0, v[0], wq[0]);
-#pragma unroll 1
-                for (int sl = 0; sl < NW; ++sl) {  // rolled: registers rotate, one channel of LDS reads in flight
-                    const int sn = sl + 1 < NW ? sl + 1 : sl;
-                    lds_fetch(sn, v[1], wq[1]);
-                    float wd[WS];
+                // (the weights are read BEFORE the values of their half: a weight carried round the loop is copied into the low half of
+                // a pair at the loop's end, and the wait in front of that copy then leaves the value reads in flight)
+                auto rd_w = [&](int sl, f32x4 (&ww)[WS / 4], float& tv) {
 #pragma unroll
                     for (int h = 0; h < WS / 4; ++h) {
-                        wd[4 * h] = wq[0][h].x; wd[4 * h + 1] = wq[0][h].y; wd[4 * h + 2] = wq[0][h].z; wd[4 * h + 3] = wq[0][h].w;
+                        const float4 x = wp4[sl * (WS / 4) + h];
+                        ww[h] = f32x4{x.x, x.y, x.z, x.w};
                     }
+                    if constexpr (GEN) tv = tp[sl * 64];  // tail column e = q of row 16t + n
+                };
+                auto mix_half = [&](int j0, const f32x4 (&hh)[2], const f32x4 (&ww)[WS / 4], float tv) {
 #pragma unroll
                     for (int dd = 0; dd < DPW; ++dd) {
+                        const float wd = ww[dd / 4][dd & 3];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            acc[dd][0][r] = fmaf(wd[dd], v[0][r].x, acc[dd][0][r]);
-                            acc[dd][1][r] = fmaf(wd[dd], v[0][r].y, acc[dd][1][r]);
-                            acc[dd][2][r] = fmaf(wd[dd], v[0][r].z, acc[dd][2][r]);
-                            acc[dd][3][r] = fmaf(wd[dd], v[0][r].w, acc[dd][3][r]);
+                        for (int jj = 0; jj < 2; ++jj) {
+#if CFD_BLOCK_MIX == 2
+                            acc[dd][j0 + jj] = cfd_fma4_bcast(acc[dd][j0 + jj], wd, hh[jj]);
+#else
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) acc[dd][j0 + jj][r] = fmaf(wd, hh[jj][r], acc[dd][j0 + jj][r]);
+#endif
+                        }
+                        if constexpr (GEN) {
+                            if (j0 == 2) tacc[dd] = fmaf(wd, tv, tacc[dd]);
                         }
                     }
-                    if constexpr (GEN) {  // tail column e = q of row 16t + n, source channel sl of this chunk
-                        const float tv = s_tail[((lb * NW + sl) * 16 + n) * 4 + q];
-#pragma unroll
-                        for (int dd = 0; dd < DPW; ++dd) tacc[dd] = fmaf(wd[dd], tv, tacc[dd]);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[0][r] = v[1][r];
-#pragma unroll
-                    for (int h = 0; h < WS / 4; ++h) wq[0][h] = wq[1][h];
-                }
+                };
+                static_assert(NW % 2 == 0, "the channel mix walks a chunk's source channels in pairs");
+                // channels sl (weights wa) and sl + 1 (wb); h0 and wa are in flight on entry.  The last pair reads its own first half
+                // again instead of a next one (peeling it off the loop makes the compiler hoist the tile loop's invariants and spill)
+                auto pair = [&](int sl) {
+                    const int sn = sl + 2 < NW ? sl + 2 : sl;
+                    rd_half(sl, 2, h1);
+                    cfd_sched_fence();
+                    mix_half(0, h0, wa, ta);
+                    cfd_sched_fence();
+                    rd_w(sl + 1, wb, tb);
+                    rd_half(sl + 1, 0, h0);
+                    cfd_sched_fence();
+                    mix_half(2, h1, wa, ta);
+                    cfd_sched_fence();
+                    rd_half(sl + 1, 2, h1);
+                    cfd_sched_fence();
+                    mix_half(0, h0, wb, tb);
+                    cfd_sched_fence();
+                    rd_w(sn, wa, ta);
+                    rd_half(sn, 0, h0);
+                    cfd_sched_fence();
+                    mix_half(2, h1, wb, tb);
+                    cfd_sched_fence();
+                };
+                rd_w(0, wa, ta);
+                rd_half(0, 0, h0);
+#pragma unroll 1
+                for (int sl = 0; sl < NW; sl += 2) pair(sl);
             }
         }
         // ---- tile epilogue: [* gelu'(aprev)], whole-float4 row stores ----
 #pragma unroll
         for (int dd = 0; dd < DPW; ++dd) {
             const int d = dbase + wave + dd * NW;
+#if CFD_BLOCK_MIX == 2
+            // (opaque: the sums leave the mix as register PAIRS, and the element-wise arithmetic below would be paired up after them --
+            // v_pk_mul_f32 / v_pk_add_f32 that pick their halves with op_sel:[0,1,..], the form build.py's lint refuses)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[dd][j] = cfd_opaque_f4(acc[dd][j]);
+#endif
             float4 ap[4];
             if constexpr (DGELU) {
 #pragma unroll
