@@ -11,6 +11,7 @@ import ctypes as C
 from typing import Optional
 
 CFD_MAX_LAYERS = 16
+CFD_CLIP_FLOATS = 1024  # floats of cfd_fno_params.clip (include/cfdbench_amd.h)
 
 
 class CfdError(RuntimeError):
@@ -30,6 +31,8 @@ class FnoParams(C.Structure):
         ("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p),
         # ABI 603, read from the `grads` struct only; NULL = not asked (include/cfdbench_amd.h)
         ("d_inputs", C.c_void_p), ("d_case_params", C.c_void_p),
+        # ABI 604, read from the `grads` struct by cfd_fno_adam_step only: gradient-norm clipping; clip = NULL: none
+        ("clip", C.c_void_p), ("max_grad_norm", C.c_float),
     ]
 
 
@@ -42,7 +45,7 @@ class FfnStackArgs(C.Structure):
 
 
 _P = C.c_void_p
-ABI_VERSION = 603  # include/cfdbench_amd.h: CFD_ABI_VERSION
+ABI_VERSION = 604  # include/cfdbench_amd.h: CFD_ABI_VERSION
 _I = C.c_int
 _F = C.c_float
 _Z = C.c_size_t

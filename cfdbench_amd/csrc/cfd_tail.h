@@ -179,6 +179,14 @@ struct StemAdamJob {
     int nrec, spl, P, in_chan, C;
     long w_off, b_off;  // element offsets of fc0.weight / fc0.bias inside the flat parameter buffer
 };
+// Gradient-norm clipping as the two launches of cfd_fno_adam_step see it: buf = cfd_fno_params.clip (buf[0] norm, buf[1] coefficient,
+// record r = the two 32-bit halves of an fp64 sum of squares at buf[2 + 2 r]: the buffer is only 4-byte aligned); NULL: no clipping
+#define CFD_CLIP_MAX_WGS 256  // flat workgroups of k_gradsq; with the lifting layer's <= 255 rows: 2 + 2 * 511 = CFD_CLIP_FLOATS
+struct ClipArgs {
+    float* buf;
+    float max_norm;
+    int nrec;
+};
 
 // Workgroup `blk` of `t.nblk` (any workgroup size that is a multiple of 64): thread-strided over the spectral elements,
 // workgroup-strided over the groups of 16 1x1-conv elements.  `scratch`: LDS of the carrying kernel, >= 16 floats per wave.
@@ -233,5 +241,9 @@ int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp,
 // Adam on the flat parameter buffer with the deferred work of the fused training step (fno.cpp: cfd_fno_adam_step): `sums` != NULL:
 // every gradient is multiplied by sums[3] / sums[2] on top of grad_scale (deferred nMSE normaliser); job.part != NULL: workgroup c < C
 // finishes the lifting layer's gradient row c from the block kernel's sum records, stores it and applies Adam to it.
+// clip != NULL (cfd_fno_params.clip, ABI 604): global gradient-norm clipping.  One launch more: k_gradsq takes the lifting layer's job over
+// (same stem_combine_channel, so the same rows), and leaves one fp64 sum of squares per workgroup in clip[2..]; every workgroup of the
+// Adam launch adds those records up in one fixed order and folds coef = min(1, max_grad_norm / (norm + 1e-6)) into the gradient scale.
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, void* stream);
+                        float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
+                        float max_grad_norm, void* stream);

@@ -455,6 +455,9 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     CFD_TRY(check_shape("cfd_fno_adam_step", p, s, act_dtype));
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
+    // grads->clip / max_grad_norm (ABI 604) are read here and nowhere else: the route does not depend on them
+    CFD_REQUIRE(!g->clip || g->max_grad_norm > 0.f, CFD_ERR_INVALID_ARG,
+                "cfd_fno_adam_step: grads->max_grad_norm must be > 0 when grads->clip is set (+inf: measure the norm, clip nothing)");
     const View v(p, s, 1, act_dtype, ws);
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
                 "cfd_fno_adam_step: grads->d_inputs / d_case_params need fp32 activation storage");
@@ -473,5 +476,5 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
         job = StemAdamJob{v.stem_part(), case_params, s->B * spl, spl, s->n_case_params, s->in_chan, s->hidden, (long)(gw - grad), (long)(gb - grad)};
     }
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                               rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, stream);
+                               rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm, stream);
 }

@@ -1552,6 +1552,99 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Global gradient-norm clipping of the fused training step (cfd_fno_params.clip, ABI 604; torch.nn.utils.clip_grad_norm_, norm_type 2).
+// The gradient is final only inside the optimiser launch (CFD_TRAIN_DEFER_*: the nMSE normaliser is a factor Adam applies, the fc0 rows
+// are finished by Adam's workgroups), so the norm is taken there: k_gradsq carries the lifting layer's job instead of k_adam_f and sums
+// squares in fp64, one record per workgroup; k_adam_f adds the records up (every workgroup the same few hundred doubles in the same
+// order, so the same coefficient) and multiplies it into the gradient scale.  No atomics: two calls give the same bits.
+// ------------------------------------------------------------------------------------------------------
+// (a record is an fp64 stored as two 32-bit words: the clip buffer is a float buffer on any 4-byte boundary)
+__device__ __forceinline__ void clip_store_f64(float* q, double d) {
+    unsigned long long u;
+    __builtin_memcpy(&u, &d, 8);
+    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
+    __builtin_memcpy(q, &lo, 4);
+    __builtin_memcpy(q + 1, &hi, 4);
+}
+__device__ __forceinline__ double clip_load_f64(const float* q) {
+    unsigned lo, hi;
+    __builtin_memcpy(&lo, q, 4);
+    __builtin_memcpy(&hi, q + 1, 4);
+    const unsigned long long u = ((unsigned long long)hi << 32) | lo;
+    double d;
+    __builtin_memcpy(&d, &u, 8);
+    return d;
+}
+// sum over the 256 threads of a workgroup, fixed tree; every thread calls it and gets the total
+__device__ __forceinline__ double clip_block_sum(double a, double (&s_sq)[256]) {
+    s_sq[threadIdx.x] = a;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h) s_sq[threadIdx.x] += s_sq[threadIdx.x + h];
+        __syncthreads();
+    }
+    return s_sq[0];
+}
+__device__ __forceinline__ double clip_total_sq(const float* __restrict__ buf, int nrec, double (&s_sq)[256]) {
+    double a = 0.0;
+    for (int r = threadIdx.x; r < nrec; r += 256) a += clip_load_f64(buf + 2 + 2 * r);
+    return clip_block_sum(a, s_sq);
+}
+
+// Workgroup c < job.C: row c of the lifting layer's gradient (what k_adam_f's workgroup c does without clipping, minus Adam) and the sum
+// of its squares; the other workgroups: the squares of the flat gradient buffer outside the lifting layer's two ranges, thread-strided,
+// four independent loads per thread and trip.  Record blockIdx.x of clip[2..] = this workgroup's sum.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gradsq(float* __restrict__ g, size_t n, float* __restrict__ clip, const StemAdamJob job) {
+    __shared__ float s_r[CFD_STEMG_NA][256];
+    __shared__ double s_sq[256];
+    const int njob = job.part ? job.C : 0;
+    const int F = job.in_chan + 3 + job.P;
+    double acc = 0.0;
+    if ((int)blockIdx.x < njob) {
+        const int c = blockIdx.x;
+        stem_combine_channel(job.part, job.nrec, job.spl, job.cp, job.P, job.C, c, s_r);
+        if ((int)threadIdx.x <= F) {
+            const bool bias = (int)threadIdx.x == F;
+            const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
+            g[bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x] = gv;
+            acc = (double)gv * gv;
+        }
+    } else {
+        const size_t jw0 = (size_t)job.w_off, jw1 = jw0 + (size_t)job.C * F, jb0 = (size_t)job.b_off, jb1 = jb0 + job.C;
+        auto mine = [&](size_t e) { return !(njob && ((e >= jw0 && e < jw1) || (e >= jb0 && e < jb1))); };
+        const size_t t0 = (size_t)(blockIdx.x - njob) * blockDim.x + threadIdx.x, nt = (size_t)(gridDim.x - njob) * blockDim.x;
+        if constexpr (VEC) {
+            const size_t n4 = n >> 2;
+            const size_t jlo = jw0 < jb0 ? jw0 : jb0, jhi = jw1 > jb1 ? jw1 : jb1;
+            for (size_t i0 = t0; i0 < n4; i0 += 4 * nt) {
+                f32x4 x[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const size_t i = i0 + u * nt;
+                    x[u] = i < n4 ? reinterpret_cast<const f32x4*>(g)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const size_t i = i0 + u * nt;
+                    const bool edge = njob && 4 * i < jhi && 4 * i + 4 > jlo;  // a unit that touches the lifting layer's ranges
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (!edge || mine(4 * i + j)) acc += (double)x[u][j] * x[u][j];
+                }
+            }
+            for (size_t i = 4 * n4 + t0; i < n; i += nt)
+                if (mine(i)) acc += (double)g[i] * g[i];
+        } else {
+            for (size_t i = t0; i < n; i += nt)
+                if (mine(i)) acc += (double)g[i] * g[i];
+        }
+    }
+    const double tot = clip_block_sum(acc, s_sq);
+    if (threadIdx.x == 0) clip_store_f64(clip + 2 + 2 * blockIdx.x, tot);
+}
+
 // Round 6, the fused training step's optimiser launch (cfd_fno_adam_step): the flat Adam above PLUS the work that used to be launches of
 // its own in front of it -- (a) the nMSE normaliser: the head ran with the mse coefficient upstream / n, so every gradient still lacks the
 // factor n / sum (label*mask)^2 = sums[3] / sums[2] (both left by the head's reduction; k_label_energy_part + _coef: two launches, 10 us);
@@ -1560,9 +1653,17 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
-                                                float gscale, const float* __restrict__ sums, const StemAdamJob job) {
+                                                float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip) {
     __shared__ float s_r[CFD_STEMG_NA][256];
+    __shared__ double s_sq[256];
     if (sums) gscale *= sums[3] / sums[2];
+    if (clip.buf) {  // (uniform; NULL = the launch of ABI 603: nothing is loaded before the first element)
+        const double sq = clip_total_sq(clip.buf, clip.nrec, s_sq);
+        const double norm = fabs((double)gscale) * sqrt(sq);
+        const double coef = n ? fmin(1.0, (double)clip.max_norm / (norm + 1e-6)) : 1.0;
+        if (blockIdx.x == 0 && threadIdx.x == 0) clip.buf[0] = (float)norm, clip.buf[1] = (float)coef;
+        gscale *= (float)coef;  // (coef == 1: the same bits as without clipping)
+    }
     const int njob = job.part ? job.C : 0;
     const int F = job.in_chan + 3 + job.P;
     if ((int)blockIdx.x < njob) {
@@ -1610,24 +1711,44 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
 }
 
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, void* stream) {
+                        float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
+                        float max_grad_norm, void* stream) {
     CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: step must be >= 1");
-    if (n == 0) return CFD_OK;
-    const StemAdamJob jb = job ? *job : StemAdamJob{};
+    CFD_REQUIRE(!clip || max_grad_norm > 0.f, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: max_grad_norm must be > 0 (+inf: measure only)");
+    if (n == 0 && !clip) return CFD_OK;
+    StemAdamJob jb = job ? *job : StemAdamJob{};
     CFD_REQUIRE(!jb.part || (jb.P <= 8 && jb.in_chan + 3 + jb.P < 256), CFD_ERR_UNSUPPORTED, "cfd_fno_adam_step: lifting layer with %d case parameters", jb.P);
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     const bool vec = ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0) && n >= 4;
     size_t blocks = ((vec ? n / 4 : n) + 255) / 256;
     if (blocks > 2048) blocks = 2048;
+    ClipArgs ca{};
+    if (clip) {  // the norm needs the finished fc0 rows: k_gradsq takes the job, Adam's launch runs the flat update alone
+        const int njob = jb.part ? jb.C : 0;
+        CFD_REQUIRE(2 + 2 * (njob + CFD_CLIP_MAX_WGS) <= CFD_CLIP_FLOATS, CFD_ERR_UNSUPPORTED,
+                    "cfd_fno_adam_step: clipping with a lifting layer of %d channels", njob);
+        const size_t gsq = n == 0 ? 0 : (blocks < CFD_CLIP_MAX_WGS ? blocks : (size_t)CFD_CLIP_MAX_WGS);
+        ca = ClipArgs{clip, max_grad_norm, (int)gsq + njob};
+        if (ca.nrec > 0) {
+            CFD_PROF_W("k_gradsq", (hipStream_t)stream, 4.0 * n, 2.0 * n);
+            if (vec)
+                hipLaunchKernelGGL(k_gradsq<true>, dim3((unsigned)ca.nrec), dim3(256), 0, (hipStream_t)stream, grad, n, clip, jb);
+            else
+                hipLaunchKernelGGL(k_gradsq<false>, dim3((unsigned)ca.nrec), dim3(256), 0, (hipStream_t)stream, grad, n, clip, jb);
+            CFD_LAUNCH_CHECK("cfd_fno_adam_step");
+        }
+        jb = StemAdamJob{};
+        if (blocks == 0) blocks = 1;  // (n == 0: one workgroup stores clip[0] = 0, clip[1] = 1)
+    }
     blocks += jb.part ? jb.C : 0;
     CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
     if (vec)
         hipLaunchKernelGGL(k_adam_f<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb);
+                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb, ca);
     else
         hipLaunchKernelGGL(k_adam_f<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb);
+                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb, ca);
     CFD_LAUNCH_CHECK("cfd_fno_adam_step");
     return CFD_OK;
 }

@@ -17,6 +17,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
+from ._capi import CFD_CLIP_FLOATS
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
@@ -254,10 +255,23 @@ def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
 
 
 class FnoTrainEngine:
+    """The fused Auto-FNO training step on flat buffers (module docstring).
+
+    What ``flat.grad`` holds after ``train_step``: the buffer the backward kernels wrote, NOT the gradient Adam applied.  With the
+    deferred single-GPU step (``defer_flags``) it lacks the nMSE normaliser ``sums[3] / sums[2]`` (Adam's launch applies that factor)
+    and its fc0 rows are written by the optimiser call itself; data-parallel, it is the SUM over ranks (Adam applies ``1 / world``);
+    and it is never clipped.  Read gradients through ``gradients()`` (loss units, unclipped) and their norm through ``grad_norm()``;
+    calling ``torch.nn.utils.clip_grad_norm_`` on the engine's views clips the wrong numbers -- pass ``max_grad_norm`` instead."""
+
     def __init__(self, model, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
-                 overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32"):
-        """``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
+                 overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None):
+        """``max_grad_norm``: global gradient-norm clipping inside the optimiser call (cfd_fno_params.clip; the semantics of
+        ``torch.nn.utils.clip_grad_norm_`` with norm_type 2, taken of the gradient Adam applies -- after the deferred normaliser, the
+        lifting layer's rows and, data-parallel, the all-reduce and its 1 / world).  None: no clipping, the calls of an engine without
+        the argument; ``float("inf")``: the norm is measured (``grad_norm()``) and nothing is clipped.  One launch more per step.
+
+        ``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
         activations a_0 .. a_L are rounded to bf16 when stored -- half the bytes of what the backward pass re-reads -- and the
         backward pass reads those rounded values; master weights, gradients, accumulation and Adam stay fp32
         (cfd_fno_forward_train_ex / cfd_fno_backward_phase_ex).  Needs the one-pass head (fused_head)."""
@@ -300,6 +314,13 @@ class FnoTrainEngine:
         self.scores_buf = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._shape_key = None
         self._graph = None
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.clip = None
+        if self.max_grad_norm is not None:
+            if not self.max_grad_norm > 0.0:  # (NaN fails the comparison too)
+                raise ValueError("max_grad_norm must be > 0 (None: no clipping, float('inf'): measure the norm only)")
+            self.clip = torch.zeros(CFD_CLIP_FLOATS, dtype=torch.float32, device=self.device)
+            self.gstruct.clip, self.gstruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
 
     # ------------------------------------------------------------------------------------------------
     def _prepare(self, inputs: Tensor, case_params: Tensor):
@@ -380,7 +401,12 @@ class FnoTrainEngine:
     def optimizer_step(self, grad_scale: float = 1.0):
         self.step_count += 1
         inputs, case_params, mask, flags = getattr(self, "_last", (None, None, None, 0))
-        if flags:  # the pass left work to this launch: nMSE normaliser from sums[2:4], the lifting layer's gradient rows
+        # the pass left work to this launch (nMSE normaliser from sums[2:4], the lifting layer's gradient rows), or the step clips: the
+        # norm is taken inside cfd_fno_adam_step, which with flags = 0 is cfd_adam_flat otherwise
+        if self.clip is not None and inputs is None:
+            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping needs the pass that produced the gradients "
+                               "(forward_backward / train_step) first")
+        if flags or self.clip is not None:
             self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
                           inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
                           self.ws.data_ptr(), self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
@@ -395,11 +421,24 @@ class FnoTrainEngine:
                       self.weight_decay, self.step_count, grad_scale, torch.cuda.current_stream().cuda_stream)
 
     def gradients(self) -> Tensor:
-        """The flat gradient of the last step in the loss's own units.  After a deferred train_step (``defer_flags``) the buffer holds the
-        gradients of sum d^2 / n -- this returns them times n / sum (label*mask)^2 (what Adam applied); otherwise the buffer itself."""
+        """The flat gradient of the last step in the loss's own units, UNCLIPPED (with ``max_grad_norm`` Adam applied it times
+        ``clip_coef()``; the buffer is never clipped).  After a deferred train_step (``defer_flags``) the buffer holds the gradients of
+        sum d^2 / n -- this returns them times n / sum (label*mask)^2; otherwise the buffer itself (data-parallel: the sum over ranks)."""
         if getattr(self, "_grad_pending_scale", False):
             return self.flat.grad * (self.sums[3] / self.sums[2])
         return self.flat.grad
+
+    def grad_norm(self) -> Tensor:
+        """0-dim device tensor (a view, no sync): the global 2-norm of the gradient the last optimiser call applied, before clipping."""
+        if self.clip is None:
+            raise RuntimeError("FnoTrainEngine.grad_norm: the engine was built without max_grad_norm (float('inf') measures without clipping)")
+        return self.clip[0]
+
+    def clip_coef(self) -> Tensor:
+        """0-dim device tensor (a view, no sync): min(1, max_grad_norm / (norm + 1e-6)) of the last optimiser call."""
+        if self.clip is None:
+            raise RuntimeError("FnoTrainEngine.clip_coef: the engine was built without max_grad_norm")
+        return self.clip[1]
 
     def train_step(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None) -> Tensor:
         """One optimisation step; returns the device tensor [sum sq err, sum abs err, sum sq label, n] of THIS rank's

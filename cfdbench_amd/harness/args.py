@@ -16,7 +16,9 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``dtype`` ("bf16": the FNO's activations between kernels are stored as bf16 -- test_multistep: BASELINE configs[4];
     train_auto --fused 1: bf16-storage training with fp32 master weights, gradients and optimiser),
     ``unroll_steps`` (train_auto, K > 1: the FNO is trained through a K-step rollout -- loss = mean nmse of K steps with every prediction
-    fed back as the next input, cfdbench_amd/unroll.py; eager autograd path only; 1 = the reference's one-step loop).
+    fed back as the next input, cfdbench_amd/unroll.py; eager autograd path only; 1 = the reference's one-step loop),
+    ``max_grad_norm`` (> 0: global gradient-norm clipping at that threshold before every optimiser step -- --fused 1: inside the engine's
+    optimiser call, eager paths: torch.nn.utils.clip_grad_norm_; 0.0 = off; not with --graph 1).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -46,7 +48,7 @@ _FLAGS: Dict[str, Any] = dict(
     lr_step_size=20, lr_gamma=0.9,
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
-    lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1,
+    lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -102,6 +104,9 @@ def is_args_valid(args: Args) -> None:
     if args.graph:
         assert not args.fused, "--graph 1 captures the autograd step; the fused FNO engine has its own launch path"
         assert args.gradient_accumulation_steps == 1, "--graph 1 captures one optimiser step per batch"
+    assert args.max_grad_norm >= 0.0, "--max_grad_norm is a threshold on the gradient's 2-norm (0 = no clipping)"
+    if args.graph:
+        assert not args.max_grad_norm > 0.0, "--graph 1 with --max_grad_norm is not built: the captured multi-tensor Adam has no clipping"
     assert args.unroll_steps >= 1, "--unroll_steps counts the model steps of one training window (1 = the one-step loop)"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:

@@ -100,14 +100,21 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
           eval_interval: int = 2, measure_time: bool = False, plot_interval: int = 1, resume: bool = False,
           lr_scheduler_kind: str = "step", lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5,
           early_stopping_patience: int = 0, early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1,
-          graph: bool = False):
+          graph: bool = False, max_grad_norm: float = 0.0):
     """src/train.py:148-253: fwd -> ``loss["nmse"].backward()`` -> Adam -> zero_grad; StepLR per epoch.
     ``graph``: the step replayed from HIP graphs (harness/train_auto.py:train has the semantics; no accumulation; several ranks: graph.py).
     ``resume``: continue from ``train_state.pt`` (see harness/train_auto.py:train).  ``lr_scheduler_kind`` /
     ``early_stopping_patience`` / ``gradient_accumulation_steps``: the same options, with the same semantics, as
-    harness/train_auto.py:train (harness/schedule.py); the defaults are the reference's loop."""
+    harness/train_auto.py:train (harness/schedule.py); the defaults are the reference's loop.  ``max_grad_norm`` > 0:
+    ``torch.nn.utils.clip_grad_norm_`` before every optimiser step (after the gradient exchange; not with ``graph``); the log line
+    then carries ``grad_norm``."""
     rank, world = _rank_world()
     output_dir = Path(output_dir)
+    clip = float(max_grad_norm) > 0.0
+    if float(max_grad_norm) < 0.0 or max_grad_norm != max_grad_norm:
+        raise ValueError("max_grad_norm must be >= 0 (0 = no clipping)")
+    if clip and graph:
+        raise NotImplementedError("--max_grad_norm needs --graph 0: the captured multi-tensor Adam step has no clipping")
     if world > 1:
         broadcast_model_state(model)
 
@@ -138,6 +145,7 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
     stopper = EarlyStopping(early_stopping_patience, early_stopping_delta)
     start_time = time.time()
     global_step = 0
+    grad_norm = None  # clipping: the last optimiser step's norm, on the device until the log line fetches it
     all_train_losses: List[float] = []
     start_ep = 0
     state_path = output_dir / "train_state.pt"
@@ -192,14 +200,19 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
             if (step + 1) % accum == 0 or step + 1 == n_steps:
                 if world > 1:
                     sync_gradients(list(model.parameters()))
+                if clip:
+                    grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
                 optimizer.step()
                 optimizer.zero_grad()
             ep_train_losses.append(loss.item())  # src/train.py:203
             global_step += 1
             if global_step % log_interval == 0 and not measure_time and rank == 0:
                 avg_loss = sum(ep_train_losses) / (len(ep_train_losses) + 1e-5)
-                print(dict(ep=ep, step=step, loss=f"{avg_loss:.3e}", lr=f"{schedule.lr:.3e}",
-                           time=round(time.time() - start_time)))
+                line = dict(ep=ep, step=step, loss=f"{avg_loss:.3e}", lr=f"{schedule.lr:.3e}")
+                if clip:
+                    line["grad_norm"] = "nan" if grad_norm is None else f"{float(grad_norm):.3e}"
+                line["time"] = round(time.time() - start_time)
+                print(line)
         if graph:
             ep_train_losses = torch.stack(ep_train_losses).tolist() if ep_train_losses else []
         if measure_time:
@@ -319,7 +332,7 @@ def main(argv=None):
               lr_scheduler_patience=args.lr_scheduler_patience,
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
-              graph=bool(args.graph))
+              graph=bool(args.graph), max_grad_norm=args.max_grad_norm)
     if "test" in args.mode and rank == 0:
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

@@ -178,7 +178,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           plot_interval: int = 1, resume: bool = False, device_loader: bool = False, lr_scheduler_kind: str = "step",
           lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5, early_stopping_patience: int = 0,
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
-          unroll_steps: int = 1):
+          unroll_steps: int = 1, max_grad_norm: float = 0.0):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     ``graph`` (autograd path; with several ranks the gradient exchange sits between two graphs, cfdbench_amd/graph.py): the step ``model(**batch) -> loss["nmse"].backward() -> Adam.step()`` is captured once
@@ -197,10 +197,20 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     and the loss the mean nmse of K model steps with every prediction fed back as the next input (cfdbench_amd/unroll.py); the gradient
     flows through the fed-back frames.  Evaluation, checkpoints and the result tree are those of K = 1.
 
+    ``max_grad_norm`` > 0: global gradient-norm clipping (2-norm over all parameters) before every optimiser step.  ``fused``: inside
+    the engine's optimiser call, where its gradient becomes final (FnoTrainEngine(max_grad_norm=)); the eager paths (any model,
+    ``unroll_steps`` included): ``torch.nn.utils.clip_grad_norm_`` after the gradient exchange, at the accumulation group's boundary.
+    Not with ``graph``.  The rank-0 log line then carries ``grad_norm`` (the norm before clipping, of the last optimiser step).
+
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
     other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop."""
     rank, world = _rank_world()
     output_dir = Path(output_dir)
+    clip = float(max_grad_norm) > 0.0
+    if float(max_grad_norm) < 0.0 or max_grad_norm != max_grad_norm:
+        raise ValueError("max_grad_norm must be >= 0 (0 = no clipping)")
+    if clip and graph:
+        raise NotImplementedError("--max_grad_norm needs --graph 0: the captured multi-tensor Adam step has no clipping")
     unroll = int(unroll_steps)
     windows = None
     if unroll > 1:
@@ -255,7 +265,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         if accum > 1:
             raise NotImplementedError("--gradient_accumulation_steps > 1 needs the autograd path (--fused 0): the engine's "
                                       "backward pass overwrites the flat gradient")
-        engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype)
+        engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None)
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -278,6 +288,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     stopper = EarlyStopping(early_stopping_patience, early_stopping_delta)
     start_time = time.time()
     global_step = 0
+    grad_norm = None  # clipping: the last optimiser step's norm, on the device until the log line fetches it
     train_losses: List[float] = []
     start_ep = 0
     state_path = output_dir / "train_state.pt"
@@ -366,6 +377,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 if (step + 1) % accum == 0 or step + 1 == n_steps:
                     if world > 1:
                         sync_gradients(list(model.parameters()))  # one flat all-reduce, DDP semantics
+                    if clip:
+                        grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
                     optimizer.step()
                     optimizer.zero_grad()
                 ep_train_losses.append(loss["nmse"].item())  # train_auto.py:260
@@ -377,8 +390,12 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                     mse_v, nmse_v = sc["mse"], sc["nmse"]
                 else:
                     mse_v, nmse_v = loss_mse.item(), loss_nmse.item()
-                print(dict(ep=ep, step=step, mse=f"{mse_v:.3e}", nmse=f"{nmse_v:.3e}", lr=f"{cur_lr:.3e}",
-                           time=round(time.time() - start_time)))
+                line = dict(ep=ep, step=step, mse=f"{mse_v:.3e}", nmse=f"{nmse_v:.3e}", lr=f"{cur_lr:.3e}")
+                if clip:  # (fetched here only, where the loss has synchronised already)
+                    gn = engine.grad_norm() if engine is not None else grad_norm
+                    line["grad_norm"] = "nan" if gn is None else f"{float(gn):.3e}"
+                line["time"] = round(time.time() - start_time)
+                print(line)
         if engine is not None or graph:
             ep_train_losses = torch.stack(ep_train_losses).tolist() if ep_train_losses else []
         schedule.epoch_end()
@@ -469,7 +486,7 @@ def main(argv=None):
               lr_scheduler_factor=args.lr_scheduler_factor, lr_scheduler_patience=args.lr_scheduler_patience,
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
-              act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps)
+              act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm)
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

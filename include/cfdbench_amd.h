@@ -59,7 +59,7 @@ extern "C" {
  * changes (500, round 5: the statistics records of cfd_conv2d_fwd_stats / cfd_batchnorm_fwd_stats are (C, slots, 4) floats since
  * round 4 -- a caller that still allocates (C, slots, 2) must fail at load time, not write out of bounds; the default of the
  * "act_pieces" knob is 3).  The Python binding refuses a library whose version differs (cfdbench_amd/_capi.py). */
-#define CFD_ABI_VERSION 603
+#define CFD_ABI_VERSION 604
 int cfd_version(void);
 const char* cfd_last_error(void);
 
@@ -511,7 +511,26 @@ typedef struct { /* device pointers, reference state_dict order (SURVEY.md 8b "C
      * cfd_tune_set("stem_fuse", 0).  The same `grads` struct goes to the forward call, every phase and cfd_fno_adam_step. */
     float* d_inputs;
     float* d_case_params;
+    /* Appended in ABI 604, read ONLY from the `grads` struct and ONLY by cfd_fno_adam_step (the forward call, the backward phases and the
+     * route rule ignore them): global gradient-norm clipping, torch.nn.utils.clip_grad_norm_(params, max_grad_norm) with norm_type 2, taken
+     * where the gradient becomes final -- inside the optimiser call, after the deferred normaliser and the lifting layer's rows:
+     *     s    = grad_scale * (CFD_TRAIN_DEFER_SCALE applies ? sums[3] / sums[2] : 1)            (fp32, as without clipping)
+     *     norm = |s| * sqrt(sum_i grad[i]^2)       (all n floats: a complex weight counts re^2 + im^2, the alignment padding is zero)
+     *     coef = min(1, max_grad_norm / (norm + 1e-6))          Adam sees grad[i] * (s * coef);  clip[0] = norm, clip[1] = coef
+     * The squares are summed in fp64 in a fixed order (no atomics: two calls give the same bits); norm and coef are formed in fp64 and
+     * rounded once when stored.  coef == 1 (max_grad_norm = +inf, or a norm below the threshold): parameters and moments are bitwise
+     * those of the call without `clip`.  The gradient buffer is left UNCLIPPED (under CFD_TRAIN_DEFER_STEM the fc0 rows are written, as
+     * without clipping).  Cost: one launch more than the unclipped call (k_gradsq: 4 bytes per element), on every route, with any flags.
+     * clip: NULL = no clipping, ABI 603 bit for bit.  Otherwise CFD_CLIP_FLOATS floats on any 4-byte boundary: [0] the total norm before
+     *   clipping, [1] the coefficient applied, the rest scratch of the call (partial records); everything the call reads there it has
+     *   written itself, so the buffer needs no initialisation.
+     * max_grad_norm: read when clip != NULL; > 0, +inf allowed (= measure the norm, clip nothing).  <= 0 or NaN: CFD_ERR_INVALID_ARG
+     *   before any launch.  n == 0: clip[0] = 0, clip[1] = 1.  A non-finite norm is reported in clip[0] and does not fault; nothing more
+     *   is promised (torch without error_if_nonfinite). */
+    float* clip;
+    float max_grad_norm;
 } cfd_fno_params;
+#define CFD_CLIP_FLOATS 1024 /* 2 + two floats per partial record: 256 workgroups of the flat sum + one per lifting-layer row (<= 255) */
 
 /* Bytes of caller-provided workspace: activations kept for backward + scratch.  training=0: forward only.   */
 size_t cfd_fno_workspace_bytes(const cfd_plan* plan, const cfd_fno_shape* shape, int training);
