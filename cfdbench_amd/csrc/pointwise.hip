@@ -663,6 +663,56 @@ __device__ __forceinline__ void cfd_ld8px(const __bf16* __restrict__ src, int px
     }
 }
 
+// eight consecutive pixels that all lie inside the plane: no bounds, no zero fill
+template <int VEC>
+__device__ __forceinline__ void cfd_ld8px_full(const float* __restrict__ src, float (&v)[8]) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float4 t = VEC == 4 ? *reinterpret_cast<const float4*>(src + 4 * k) : cfd_ld4u(src + 4 * k);
+        v[4 * k] = t.x; v[4 * k + 1] = t.y; v[4 * k + 2] = t.z; v[4 * k + 3] = t.w;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void cfd_ld8px_full(const __bf16* __restrict__ src, float (&v)[8]) {
+    if constexpr (VEC == 4) {
+        const bf16x8 t = *reinterpret_cast<const bf16x8*>(src);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)src[j];
+    }
+}
+
+// tail of the weight-gradient kernels: block reduction of the 4 waves' accumulator tiles, then one partial record per block
+template <int MT, int NT>
+__device__ __forceinline__ void cfd_wgrad_store_partial(const f32x4 (&acc)[MT][NT], float* s_red, float* __restrict__ part, int Ci, int Co) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int a = 0; a < MT; ++a)
+#pragma unroll
+        for (int c = 0; c < NT; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s_red[((wave * MT * NT + a * NT + c) * 4 + r) * 64 + lane] = acc[a][c][r];
+    __syncthreads();
+    // partials are stored BLOCK-major, part[block][Co (Ci + 1)] (round 5): a wave's stores are runs of consecutive elements.  (Rounds 1-4:
+    // element-major, "the scattered 4-byte stores cost the producer nothing" -- they were 0.43 M write transactions per launch, 13 MB of
+    // counted write traffic for 1.7 MB of partial sums; cfd_record_sum16 has the numbers.)
+    const int NW = Ci + 1;
+    float* dst = part + (size_t)blockIdx.x * Co * NW;
+    for (int e = threadIdx.x; e < MT * NT * 4 * 64; e += blockDim.x) {
+        const int ln = e & 63, r = (e >> 6) & 3, tile = e >> 8;
+        const int a = tile / NT, c = tile % NT;
+        const int o = 16 * a + 4 * (ln >> 4) + r, i = 16 * c + (ln & 15);
+        if (o < Co && i < NW) {
+            float s = 0.f;
+#pragma unroll
+            for (int wv = 0; wv < 4; ++wv) s += s_red[((wv * MT * NT + tile) * 4 + r) * 64 + ln];
+            dst[(size_t)(o * NW + i)] = s;
+        }
+    }
+}
+
 // TIN: storage type of `in` (float; __bf16 for the saved activations of bf16-storage training -- the gradient `g` is always fp32)
 template <int MT, int NT, int VEC, bool ACT, bool STEM, typename TIN, int AP>
 __global__ __launch_bounds__(256) void k_chan_wgrad(const float* __restrict__ g, const TIN* __restrict__ in,
@@ -808,31 +858,150 @@ __global__ __launch_bounds__(256) void k_chan_wgrad(const float* __restrict__ g,
             for (int j = 0; j < 8; ++j) bv[c][j] = bvn[c][j];
         ch = nx;
     }
-    // block reduction of the 4 waves, then one partial tile per block
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int c = 0; c < NT; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_red[((wave * MT * NT + a * NT + c) * 4 + r) * 64 + lane] = acc[a][c][r];
-    __syncthreads();
-    // partials are stored BLOCK-major, part[block][Co (Ci + 1)] (round 5): a wave's stores are runs of consecutive elements.  (Rounds 1-4:
-    // element-major, "the scattered 4-byte stores cost the producer nothing" -- they were 0.43 M write transactions per launch, 13 MB of
-    // counted write traffic for 1.7 MB of partial sums; cfd_record_sum16 has the numbers.)
-    const int NW = Ci + 1;
-    float* dst = part + (size_t)blockIdx.x * Co * NW;
-    const size_t nb = 1;
-    for (int e = threadIdx.x; e < MT * NT * 4 * 64; e += blockDim.x) {
-        const int ln = e & 63, r = (e >> 6) & 3, tile = e >> 8;
-        const int a = tile / NT, c = tile % NT;
-        const int o = 16 * a + 4 * (ln >> 4) + r, i = 16 * c + (ln & 15);
-        if (o < Co && i < NW) {
-            float s = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) s += s_red[((wv * MT * NT + tile) * 4 + r) * 64 + ln];
-            dst[(size_t)(o * NW + i) * nb] = s;
+    cfd_wgrad_store_partial<MT, NT>(acc, s_red, part, Ci, Co);
+}
+
+// The same sums at 17 .. 24 channels on both sides (MT = NT = 2, no generated columns but the ones column), where the second
+// 16-row tile of either operand holds only Co - 16 / Ci - 16 <= 16 / G channels: per chunk the kernel above loads, activates and
+// splits it with 4 (G = 4: 17 .. 20 channels) or 8 (G = 2: 21 .. 24) of every 16 lanes live.  Here a wave takes its chunks
+// ch, ch + stride, .. in groups of G: ONCE per group lane (q, n) loads pixels 8q .. 8q+7 of channel 16 + n % (16 / G) of the
+// group's chunk n / (16 / G) for both operands, so that the GELU and the split of the second tiles run with every lane live,
+// and chunk k of the group gets its channels into lanes 0 .. 16 / G - 1 by a lane exchange (cfd_shfl_xor over k 16 / G lanes,
+// applied in place: the pieces move by 16 / G, 3 * 16 / G, 16 / G lanes from chunk to chunk).  Lanes past the live count then hold
+// other chunks' channels: they feed accumulator rows o >= Co and columns i > Ci only, which are never stored (a row / column of
+// the product depends on its own operand lanes alone).  The ones column (lane Ci - 16 of the input's second tile) IS stored -- the
+// bias gradient -- and is put in per chunk: the pieces of 1.0 (0x3f80, 0, 0) for pixels below HW, zeros beyond.
+// The first tiles (channels 0 .. 15) stay per chunk, in two register sets that swap roles by name (the loop is unrolled over the
+// group; the kernel above copies 32 registers per chunk); one chunk and one group of second tiles are in flight ahead.  Every
+// accumulator receives the MFMAs of the kernel above, in its order, and none for a chunk slot past `total`: the partial records
+// are bit-identical.  B = 256, C = 20, 64 x 64 on MI355X: 37.5 -> 34.4 us, with GELU 46.1 -> 38.0 us (LABNOTES.md has the
+// instruction counts).
+template <int G, int VEC, bool ACT, typename TIN, int AP>
+__global__ __launch_bounds__(256, 4) void k_chan_wgrad_grp(const float* __restrict__ g, const TIN* __restrict__ in,
+                                                        float* __restrict__ part, int B, int Ci, int Co, int HW) {
+    static_assert(G == 2 || G == 4, "chunks per group");
+    constexpr int LPC = 16 / G;  // lanes (of 16) per chunk of the group
+    __shared__ float s_red[4 * 2 * 2 * 4 * 64];
+    const int lane = threadIdx.x & 63, wave = cfd_uniform((int)(threadIdx.x >> 6));  // chunk indices live in scalar registers
+    const int q = lane >> 4, n = lane & 15;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[2][2] = {{zero, zero}, {zero, zero}};
+    const int cpb = (HW + 31) / 32;
+    const int total = B * cpb;  // < 2^30 (checked by the launcher)
+    const int stride = (int)gridDim.x * 4;
+    const bool ones = n == Ci - 16;
+    // first tiles of one chunk.  The chunk index is wave-uniform: batch entry and pixel offset are scalar, the lane adds a constant
+    // offset (row n, pixels 8q ..), and a chunk that lies inside its plane (every chunk when HW % 32 == 0) is read without bounds.
+    // remc = HW - (the chunk's first pixel): the ones column is valid for the lane's pixels j < remc - 8q.
+    const unsigned offa = (unsigned)(n * HW + 8 * q) * 4u, offb = (unsigned)(n * HW + 8 * q) * (unsigned)sizeof(TIN);  // < 2^31 (launcher)
+    auto load1 = [&](int ch, float (&av)[8], float (&bv)[8], int& remc) {
+        const int b = (int)((unsigned)ch / (unsigned)cpb);
+        const int pxc = (ch - b * cpb) * 32;
+        remc = HW - pxc;
+        const float* ga_ = reinterpret_cast<const float*>(reinterpret_cast<const char*>(g + ((size_t)b * Co * HW + pxc)) + offa);
+        const TIN* gb_ = reinterpret_cast<const TIN*>(reinterpret_cast<const char*>(in + ((size_t)b * Ci * HW + pxc)) + offb);
+        if (remc >= 32) {
+            cfd_ld8px_full<VEC>(ga_, av);
+            cfd_ld8px_full<VEC>(gb_, bv);
+        } else {
+            cfd_ld8px<VEC>(ga_, pxc + 8 * q, HW, true, av);
+            cfd_ld8px<VEC>(gb_, pxc + 8 * q, HW, true, bv);
         }
+    };
+    // second tiles of the G chunks from `ch` on (slots past `total` and channels past Co / Ci read as zero)
+    auto loadg = [&](int ch, float (&av)[8], float (&bv)[8]) {
+        // (once per group: its lane constants are recomputed here instead of living in registers across the chunk loop)
+        const int nn = cfd_opaque(n), cc = 16 + (nn & (LPC - 1));
+        const int cs = ch + (nn / LPC) * stride;  // < 2^30 + 3 * 4096
+        const bool ok = cs < total;
+        const int b = ok ? (int)((unsigned)cs / (unsigned)cpb) : 0;
+        const int px = ok ? (cs - b * cpb) * 32 + 8 * cfd_opaque(q) : 0;
+        cfd_ld8px<VEC>(g + (((size_t)b * Co + (cc < Co ? cc : 0)) * HW + px), px, HW, ok && cc < Co, av);
+        cfd_ld8px<VEC>(in + (((size_t)b * Ci + (cc < Ci ? cc : 0)) * HW + px), px, HW, ok && cc < Ci, bv);
+    };
+    auto gelu8 = [](float (&v)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) { const cfd_f2 g2 = cfd_gelu2(cfd_f2{v[j], v[j + 1]}); v[j] = g2.x; v[j + 1] = g2.y; }
+    };
+    CfdAct8<AP> gas, gbs;  // second-tile pieces of the current group, rotated in place from chunk to chunk
+    auto rotate = [&](CfdAct8<AP>& s, int mask) {
+#pragma unroll
+        for (int p = 0; p < AP; ++p) {
+            const cfd_u32x4 w = __builtin_bit_cast(cfd_u32x4, s.p[p]);
+            cfd_u32x4 r;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned u = w[j];
+                r[j] = __builtin_bit_cast(unsigned, cfd_shfl_xor(__builtin_bit_cast(float, u), mask));
+            }
+            s.p[p] = __builtin_bit_cast(bf16x8, r);
+        }
+    };
+    // chunk k of the group: raw first tiles in av / bv
+    auto step = [&](int k, float (&av)[8], float (&bv)[8], int remc) {
+        const int rem = remc >= 32 ? 8 : remc - 8 * q;
+        if constexpr (ACT) gelu8(bv);
+        CfdAct8<AP> as[2], bs[2];
+        as[0] = cfd_act_split8<AP>(av);
+        bs[0] = cfd_act_split8<AP>(bv);
+        if (k > 0) {
+            rotate(gas, (k ^ (k - 1)) * LPC);
+            rotate(gbs, (k ^ (k - 1)) * LPC);
+        }
+        as[1] = gas;
+#pragma unroll
+        for (int p = 0; p < AP; ++p) {
+            const cfd_u32x4 w = __builtin_bit_cast(cfd_u32x4, gbs.p[p]);
+            cfd_u32x4 r;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned u = w[j];
+                const unsigned one = p == 0 ? (rem > 2 * j ? 0x3f80u : 0u) | (rem > 2 * j + 1 ? 0x3f800000u : 0u) : 0u;
+                r[j] = ones ? one : u;
+            }
+            bs[1].p[p] = __builtin_bit_cast(bf16x8, r);
+        }
+#pragma unroll
+        for (int t = 0; t < cfd_nterm_aa(AP); ++t)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    acc[a][c] = cfd_mfma16x16x32_bf16(as[a].p[cfd_term_aa_a(AP, t)], bs[c].p[cfd_term_aa_b(AP, t)], acc[a][c]);
+    };
+    float a0[8], b0[8], a1[8], b1[8], ga[8], gb[8];
+    int r0 = 0, r1 = 0;
+    int ch = (int)blockIdx.x * 4 + wave;
+    if (ch < total) {
+        load1(ch, a0, b0, r0);
+        loadg(ch, ga, gb);
     }
+    while (ch < total) {
+        if constexpr (ACT) gelu8(gb);
+        gas = cfd_act_split8<AP>(ga);
+        gbs = cfd_act_split8<AP>(gb);
+#pragma unroll
+        for (int k = 0; k < G; k += 2) {
+            int cur = ch + k * stride;
+            if (cur >= total) break;
+            if (cur + stride < total) load1(cur + stride, a1, b1, r1);
+            cfd_sched_fence();
+            step(k, a0, b0, r0);
+            cfd_sched_fence();
+            cur += stride;
+            if (cur >= total) break;
+            if (cur + stride < total) load1(cur + stride, a0, b0, r0);
+            cfd_sched_fence();
+            step(k + 1, a1, b1, r1);
+            cfd_sched_fence();
+        }
+        // the next group's second tiles (nothing is read for a slot past `total`), issued behind the group's last MFMAs: the 16 raw
+        // registers then never live beside the 24 piece registers of the group and the kernel keeps 128 registers, four workgroups
+        // per CU, without scratch (issued at the top of the group: 158 registers, three workgroups per CU, and slower -- LABNOTES.md)
+        loadg(ch + G * stride, ga, gb);
+        ch += G * stride;
+    }
+    cfd_wgrad_store_partial<2, 2>(acc, s_red, part, Ci, Co);
 }
 
 // Workgroup = 16 consecutive output elements of the block-major partial records (cfd_record_sum16): fixed summation order, deterministic.
@@ -842,7 +1011,9 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
     chan_wgrad_reduce_group(blockIdx.x, part, nblk, gw, gb, Co, Ci, s_scr);
 }
 
-static int wgrad_blocks(int B, int HW) {
+// Workgroups a launch would use without the test cap below: the workspace is sized by this figure, so the cap can be set or lifted
+// at any time without a launch ever outgrowing a workspace.
+static int wgrad_blocks_uncapped(int B, int HW) {
     const long chunks = (long)B * ((HW + 31) / 32);
     long blocks = (chunks + 7) / 8;    // >= 2 chunks per wave (one in flight while one is on the matrix pipe)
     if (blocks > 1024) blocks = 1024;  // 4 workgroups per CU (measured best of 512 / 1024 / 2048 at B = 256)
@@ -853,10 +1024,16 @@ static int wgrad_blocks(int B, int HW) {
     return (int)blocks;
 }
 
+static int wgrad_blocks(int B, int HW) {
+    const int blocks = wgrad_blocks_uncapped(B, HW);
+    const int cap = cfd_tune_get(CFD_TUNE_CHAN_WGRAD_BLOCKS);  // tests: many chunks per wave at small sizes; only ever fewer workgroups
+    return (cap > 0 && blocks > cap) ? cap : blocks;
+}
+
 extern "C" size_t cfd_chan_wgrad_workspace_bytes(int B, int Ci, int Co, int HW) {
     if (B <= 0) return 0;
     if (Ci > 32 || Co > 32) return cfd_int_wide_chan_wgrad_workspace_bytes(B, Ci, Co, HW);  // wide.hip
-    return (size_t)wgrad_blocks(B, HW) * Co * (Ci + 1) * sizeof(float);
+    return (size_t)wgrad_blocks_uncapped(B, HW) * Co * (Ci + 1) * sizeof(float);
 }
 
 // `defer` (may be NULL): leave the partial-sum reduction to a later launch (cfd_tail.h) instead of launching it here
@@ -888,11 +1065,32 @@ static int launch_wgrad(const float* g, const TIN* in, StemSrc ss, float* gw, fl
         else if (vec == 2) { if constexpr (sizeof(TIN) == 4) { if (act) CFD_WG(M_, N_, 2, true); else CFD_WG(M_, N_, 2, false); } } \
         else { if (act) CFD_WG(M_, N_, 1, true); else CFD_WG(M_, N_, 1, false); }             \
     } while (0)
+    // 17 .. 24 channels on both sides: the second tiles once per group of 4 (up to 20 channels) or 2 chunks (k_chan_wgrad_grp);
+    // chan_wgrad_grp = 0 keeps these shapes on the per-chunk kernel.  The stem's generated columns sit in the tile: per chunk.
+    // (HW < 2^24: the kernel adds a 32-bit lane offset of up to 16 planes to a scalar chunk address.)
+    const int grp = (STEM || MT != 2 || NT != 2 || Ci < 17 || Co < 17 || Ci > 24 || Co > 24 || HW >= (1 << 24) || cfd_tune_get(CFD_TUNE_CHAN_WGRAD_GRP) == 0) ? 0
+                    : (Ci <= 20 && Co <= 20)                                                                                              ? 4
+                                                                                                                                          : 2;
+#define CFD_WGG_P(G_, V_, A_, P_) \
+    hipLaunchKernelGGL((k_chan_wgrad_grp<G_, V_, A_, TIN, P_>), dim3(blocks), dim3(256), 0, st, g, in, part, B, Ci, Co, HW)
+#define CFD_WGG(G_, V_, A_)                                                                \
+    do {                                                                                   \
+        if constexpr (sizeof(TIN) == 4) { if (ap3) CFD_WGG_P(G_, V_, A_, 3); else CFD_WGG_P(G_, V_, A_, 2); } \
+        else CFD_WGG_P(G_, V_, A_, 2);                                                     \
+    } while (0)
+#define CFD_WGG_VA(G_)                                                                     \
+    do {                                                                                   \
+        if (vec == 4) { if (act) CFD_WGG(G_, 4, true); else CFD_WGG(G_, 4, false); }       \
+        else if (vec == 2) { if constexpr (sizeof(TIN) == 4) { if (act) CFD_WGG(G_, 2, true); else CFD_WGG(G_, 2, false); } } \
+        else { if (act) CFD_WGG(G_, 1, true); else CFD_WGG(G_, 1, false); }                \
+    } while (0)
     {
     // stem: the gradient tensor + the raw input channels (features are generated); otherwise gradient + activation
-    CFD_PROF_W(STEM ? "k_chan_wgrad_stem" : "k_chan_wgrad", st, (double)B * HW * (4.0 * Co + sizeof(TIN) * (STEM ? 3 : Ci)),
+    CFD_PROF_W(STEM ? "k_chan_wgrad_stem" : grp ? "k_chan_wgrad_grp" : "k_chan_wgrad", st, (double)B * HW * (4.0 * Co + sizeof(TIN) * (STEM ? 3 : Ci)),
                2.0 * B * HW * (double)Co * (Ci + 1));
-    if (MT == 1 && NT == 1) CFD_WG_VA(1, 1);
+    if (grp == 4) { if constexpr (!STEM) CFD_WGG_VA(4); }
+    else if (grp == 2) { if constexpr (!STEM) CFD_WGG_VA(2); }
+    else if (MT == 1 && NT == 1) CFD_WG_VA(1, 1);
     else if (MT == 1 && NT == 2) CFD_WG_VA(1, 2);
     else if (MT == 2 && NT == 1) CFD_WG_VA(2, 1);
     else if (MT == 2 && NT == 2) CFD_WG_VA(2, 2);
@@ -903,6 +1101,9 @@ static int launch_wgrad(const float* g, const TIN* in, StemSrc ss, float* gw, fl
         return CFD_ERR_UNSUPPORTED;
     }
     }
+#undef CFD_WGG_VA
+#undef CFD_WGG
+#undef CFD_WGG_P
 #undef CFD_WG_VA
 #undef CFD_WG
 #undef CFD_WG_P

@@ -50,6 +50,8 @@ Knob g_knobs[CFD_TUNE_COUNT] = {
     {CFD_TUNE_MODE_BC, "mode_bc", "CFD_MODE_BC", {-1}},            // batch entries per chunk of the modes.hip kernels (tests: several chunks and ragged stages at small batches)
     {CFD_TUNE_STEM_DFT, "stem_dft", "CFD_STEM_DFT", {-1}},          // the lifting layer fused into the first forward transform (k_dft_fwd64_b3<.., STEM>, round 6; 64 x 64, in_chan 2): default below 128 batch entries (rollouts), 1 = always, 0 = never
     {CFD_TUNE_GEMM_B3, "gemm_b3", "CFD_GEMM_B3", {-1}},            // 0 = tall Linear products (M >= 4096, N, K <= 1024) stay on the fp32 MFMA kernel k_gemm instead of the three-piece bf16 kernel k_rowgemm6 (round 6); 2 = k_rowgemm6 at any row count (tests)
+    {CFD_TUNE_CHAN_WGRAD_GRP, "chan_wgrad_grp", "CFD_CHAN_WGRAD_GRP", {-1}},  // 0 = the 1x1 weight gradient at 17 .. 24 channels on the per-chunk kernel k_chan_wgrad instead of k_chan_wgrad_grp (second tiles once per group of chunks); same bits
+    {CFD_TUNE_CHAN_WGRAD_BLOCKS, "chan_wgrad_blocks", "CFD_CHAN_WGRAD_BLOCKS", {-1}},  // workgroup cap of the 1x1 weight gradient (tests: several chunks and ragged groups per wave at small sizes); the workspace size ignores it
 };
 std::once_flag g_once;
 void read_env() {
