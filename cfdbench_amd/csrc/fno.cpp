@@ -109,6 +109,10 @@ int check_shape(const char* fn, const cfd_plan* p, const cfd_fno_shape* s, int d
     CFD_REQUIRE(!p->many || dt == CFD_DT_F32, CFD_ERR_UNSUPPORTED,
                 "%s: grid %dx%d, modes (%d,%d): bf16 activation storage needs modes1 <= 15, modes2 <= 16 and W <= 80", fn, p->H, p->W, p->m1,
                 p->m2);
+    // (only the general-width transforms read and write 2-byte activations, and their tables exist up to 70 rows: refused here, before
+    // the lifting layer has written the workspace, not where the first transform would find no table)
+    CFD_REQUIRE(dt == CFD_DT_F32 || (p->d_fwd_g && p->d_inv_g), CFD_ERR_UNSUPPORTED,
+                "%s: grid %dx%d: bf16 activation storage needs H <= 70 and W <= 80", fn, p->H, p->W);
     // Grids wider than 80 columns: the pixel-domain kernels index activations with 32-bit products of at most B * max(hidden, head) * H * W
     // elements (at 128 x 128 and head width 128: B <= 1023): refuse what would wrap
     if (p->W > 80) {

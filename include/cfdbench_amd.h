@@ -545,7 +545,8 @@ int cfd_fno_forward(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_
  * 200-step rollout of src/test_multistep.py:135-177 with bf16 storage): act_dtype 0 = fp32 (== cfd_fno_forward), 1 = bf16
  * (the lifting layer's output and every FnoBlock's pre-activation are rounded to bf16 when stored; inputs, predictions, kept
  * modes, weights, arithmetic and accumulation stay fp32).  cfd_fno_forward_ex(bf16) is the inference path (training must be 0);
- * bf16-storage TRAINING goes through cfd_fno_forward_train_ex / cfd_fno_backward_phase_ex below.  Grids up to 70 x 80.       */
+ * bf16-storage TRAINING goes through cfd_fno_forward_train_ex / cfd_fno_backward_phase_ex below.  Grids up to 70 x 80; a taller or
+ * wider plan, or one with more than 15 x 16 modes, is refused with CFD_ERR_UNSUPPORTED before anything is launched.           */
 size_t cfd_fno_workspace_bytes_ex(const cfd_plan* plan, const cfd_fno_shape* shape, int training, int act_dtype);
 int cfd_fno_forward_ex(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params,
                        const float* inputs, const float* case_params, const float* mask, const float* label,

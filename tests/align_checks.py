@@ -333,6 +333,12 @@ ROWS = [
     Row("modes_train_step", MK.check_train_step_deferred, (), tol(1e-9, bitwise=0.0), kw=dict(B=1, C=6, L=1, H=64, W=64, m1=20, m2=20),
         each=False, place4={4: 8, 5: 8, 11: 8, 12: 8}),
     Row("modes_refusals", MK.check_refusals, (), all_true, each=False),
+    # ---- tests/range_checks.py: shifted buffers put the transforms on their scalar-load forms; these rows take them to a tall grid (the
+    #      generic k_dft_fwd / k_idft at T = 6), to a grid with the Nyquist column (NJG = 1) and to the widest grid with 64-column tables,
+    #      at full modes (NJ = 5: scalar loads wherever the buffers lie) ------------------------------------------------------------
+    Row("range_tall_idft_epilogues", K.check_idft_epilogues, (3, 96, 64, 12, 12), tol(T)),
+    Row("range_nyquist_spectral", K.check_spectral, (1, 2, 3, 16, 16, 8, 9), tol(T)),
+    Row("range_block_grid_idft_epilogues", K.check_idft_epilogues, (3, 80, 68, 15, 16), tol(T)),
     Row("chan_head_fwd", WK.check_head_fwd, (2, 20, 152, 1), head_fwd, kw=dict(Co=3)),
     Row("chan_head_3", CK.check_head, (2, 20, 152, 0, 3, "nmse"), chan_head, emul_each=True),
     Row("chan_head_8", CK.check_head, (2, 20, 152, 1, 8, "mse"), chan_head),

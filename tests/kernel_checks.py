@@ -484,18 +484,18 @@ def check_fno_vs_oracle(be, B, C, L, H, W, p=5, border=False, gain=4.0, pseed=7,
     return res
 
 
-def check_fno_bf16_storage(be, B, C, L, H, W, p=5, border=True, gain=4.0, pseed=17, bseed=18):
+def check_fno_bf16_storage(be, B, C, L, H, W, p=5, border=True, gain=4.0, pseed=17, bseed=18, m1=12, m2=12):
     """cfd_fno_forward_ex with bf16 activation storage (BASELINE configs[4]) against the oracle with the SAME storage rule:
     the lifting layer's output and every FnoBlock's pre-activation rounded to bf16 (RNE) where they are stored, everything
     else fp32 / fp64.  An fp32 value that sits within round-off of a bf16 rounding boundary may fall to the other side than
     the fp64 oracle's (one element in ~2e4, one bf16 ulp each), which bounds the agreement near 1e-9; ``vs_f32`` reports how
     far the bf16-storage predictions are from the fp32 path (the price of the storage format, not an error)."""
     api, P = be.api, be.ptr
-    params = synth.make_fno_params(pseed, C, L, 12, 12, p, spectral_gain=gain)
+    params = synth.make_fno_params(pseed, C, L, m1, m2, p, spectral_gain=gain)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=border)
-    plan = api.plan_create(H, W, 12, 12)
+    plan = api.plan_create(H, W, m1, m2)
     try:
-        shape = FnoShape(B, H, W, 2, 2, p, C, L, 12, 12, 128)
+        shape = FnoShape(B, H, W, 2, 2, p, C, L, m1, m2, 128)
         pd = {k: be.dev(v) for k, v in params.items()}
         ps = make_param_struct(be, pd, L)
         di, dc, dm, dl = (be.dev(batch[k]) for k in ("inputs", "case_params", "mask", "label"))

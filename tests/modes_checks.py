@@ -20,16 +20,26 @@ nm = K.nm
 WHICH = {"mse": 0, "nmse": 1, "mae": 2}
 
 
+def oracle_step(params, batch, L, which="nmse"):
+    """(forward result, {parameter: gradient}) of the fp64 oracle for one batch.  The reference must be a number before anything is held
+    to it: a batch whose mask leaves no pixel makes the oracle's own nMSE 0/0, and that is the caller's mistake, not a result."""
+    p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
+    b64 = {k: v.astype(f64) for k, v in batch.items()}
+    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
+    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
+    assert np.isfinite(ref["loss"][which]) and np.all(np.isfinite(ref["preds"])), f"the oracle's own {which} loss / predictions are not finite"
+    bad = [k for k, g in rg.items() if not np.all(np.isfinite(g))]
+    assert not bad, f"the oracle's own gradients are not finite: {bad}"
+    return ref, rg
+
+
 def check_fno_vs_oracle(be, B, C, L, H, W, m1, m2, p=5, border=True, gain=4.0, pseed=7, bseed=8):
     """Whole model at modes (m1, m2) against the fp64 oracle: predictions (training and inference workspaces), the nMSE loss and every
     parameter gradient."""
     params = synth.make_fno_params(pseed, C, L, m1, m2, p, spectral_gain=gain)
     batch = synth.make_batch(bseed, B, H, W, p, border_mask=border)
     out = F.run_fno(be, params, batch, L, C, H, W, p, m1, m2)
-    p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
-    b64 = {k: v.astype(f64) for k, v in batch.items()}
-    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
-    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], "nmse"), L)
+    ref, rg = oracle_step(params, batch, L)
     res = {"preds": nm(out["preds"], ref["preds"]), "preds_infer": nm(out["preds_infer"], ref["preds"])}
     res["nmse_loss"] = abs(out["scores"][3] - ref["loss"]["nmse"]) / ref["loss"]["nmse"]
     for k in params:
@@ -46,10 +56,7 @@ def check_train_step_deferred(be, B, C, L, H, W, m1, m2, p=5, which="mse", flags
     out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, m1, m2, which=which, flags=flags, steps=steps)
     a, b = out[0], out[flags]
     res = {"bitwise": K.nan_max(*[np.max(np.abs(a[k] - b[k])) for k in ("flat", "g1", "sums1", "preds1")])}
-    p64 = {k: v.astype(c128 if np.iscomplexobj(v) else f64) for k, v in params.items()}
-    b64 = {k: v.astype(f64) for k, v in batch.items()}
-    ref = O.fno_forward(p64, b64["inputs"], b64["case_params"], b64["mask"], b64["label"], L)
-    rg = O.fno_backward(p64, ref["cache"], O.loss_grad_wrt_preds(ref["cache"]["preds"], ref["cache"]["label"], which), L)
+    _ref, rg = oracle_step(params, batch, L, which)
     for k in layout:
         res["oracle:" + k] = nm(F.flat_slice(b["g1"], layout, k), F.flat_view(rg[k]))
     return res
