@@ -12,6 +12,9 @@ from typing import Optional
 
 CFD_MAX_LAYERS = 16
 CFD_CLIP_FLOATS = 1024  # floats of cfd_fno_params.clip (include/cfdbench_amd.h)
+# bits of cfd_fno_adam_step's `flags` beside CFD_TRAIN_DEFER_* (1, 2, 4): gradient accumulation over micro-batches
+CFD_STEP_ACCUMULATE = 8   # param = an accumulator laid out like grad: param[i] = fmaf(s, grad[i], param[i]) instead of Adam
+CFD_STEP_ACCUM_INIT = 16  # with CFD_STEP_ACCUMULATE: param[i] = s * grad[i], the previous contents are never read
 
 
 class CfdError(RuntimeError):

@@ -247,3 +247,7 @@ int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp,
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
                         float max_grad_norm, void* stream);
+// CFD_STEP_ACCUMULATE of cfd_fno_adam_step: the same deferred work (`sums`, `job`), but acc[i] = s * grad[i] (init) or fmaf(s, grad[i], acc[i])
+// instead of Adam; `acc` is laid out like `grad` (k_grad_accum, pointwise.hip)
+int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,
+                         void* stream);

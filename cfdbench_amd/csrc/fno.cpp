@@ -459,8 +459,14 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     CFD_TRY(check_shape("cfd_fno_adam_step", p, s, act_dtype));
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
+    // CFD_STEP_ACCUMULATE: `param` is an accumulator laid out like `grad`; the call finishes the pass's gradient and adds it instead of
+    // running Adam (the moments, the hyper-parameters and grads->clip are not read)
+    const bool accumulate = (flags & CFD_STEP_ACCUMULATE) != 0;
+    CFD_REQUIRE(accumulate || !(flags & CFD_STEP_ACCUM_INIT), CFD_ERR_INVALID_ARG,
+                "cfd_fno_adam_step: CFD_STEP_ACCUM_INIT without CFD_STEP_ACCUMULATE");
+    if (accumulate && n == 0) return CFD_OK;  // (an empty accumulator: nothing to finish, nothing to add)
     // grads->clip / max_grad_norm (ABI 604) are read here and nowhere else: the route does not depend on them
-    CFD_REQUIRE(!g->clip || g->max_grad_norm > 0.f, CFD_ERR_INVALID_ARG,
+    CFD_REQUIRE(accumulate || !g->clip || g->max_grad_norm > 0.f, CFD_ERR_INVALID_ARG,
                 "cfd_fno_adam_step: grads->max_grad_norm must be > 0 when grads->clip is set (+inf: measure the norm, clip nothing)");
     const View v(p, s, 1, act_dtype, ws);
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
@@ -476,9 +482,15 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
                     "cfd_fno_adam_step: grads->fc0 does not point into the flat gradient buffer");
         CFD_REQUIRE((const float*)prm->fc0_w - param == gw - grad && (const float*)prm->fc0_b - param == gb - grad, CFD_ERR_INVALID_ARG,
                     "cfd_fno_adam_step: params and grads are laid out differently");
+        const size_t w_end = (size_t)(gw - grad) + (size_t)s->hidden * (s->in_chan + 3 + s->n_case_params), b_end = (size_t)(gb - grad) + s->hidden;
+        CFD_REQUIRE(!accumulate || (w_end <= n && b_end <= n), CFD_ERR_INVALID_ARG,
+                    "cfd_fno_adam_step: grads->fc0 reaches past the flat gradient buffer");
         const int spl = cfd_int_stemg_splits(p, s->B);
         job = StemAdamJob{v.stem_part(), case_params, s->B * spl, spl, s->n_case_params, s->in_chan, s->hidden, (long)(gw - grad), (long)(gb - grad)};
     }
+    if (accumulate)
+        return cfd_int_grad_accum_f(param, grad, n, grad_scale, rt.scale ? sums : nullptr, rt.stem ? &job : nullptr,
+                                    (flags & CFD_STEP_ACCUM_INIT) != 0, stream);
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm, stream);
 }

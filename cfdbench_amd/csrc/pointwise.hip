@@ -1954,6 +1954,87 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
     return CFD_OK;
 }
 
+// Gradient accumulation over micro-batches (CFD_STEP_ACCUMULATE of cfd_fno_adam_step): the optimiser launch's place in a pass that is not
+// the group's last.  It finishes the pass's gradient exactly as k_adam_f does -- the deferred normaliser in the scale, workgroup c < job.C
+// the lifting layer's row c, stored into g in the pass's unscaled units -- and its update rule is acc[i] = s * g[i] (INIT: the previous
+// contents are never loaded) or fmaf(s, g[i], acc[i]).  One thread writes each element, no atomics: two calls give the same bits.  12 bytes
+// per element, 8 with INIT; the flat part is k_adam_f's loop (one f32x4 of each buffer per thread and trip, grid capped like Adam's).
+template <bool VEC, bool INIT>
+__global__ __launch_bounds__(256) void k_grad_accum(float* __restrict__ acc, float* __restrict__ g, size_t n, float gscale,
+                                                    const float* __restrict__ sums, const StemAdamJob job) {
+    __shared__ float s_r[CFD_STEMG_NA][256];
+    if (sums) gscale *= sums[3] / sums[2];
+    auto add = [&](float& a, float gv) { a = INIT ? gscale * gv : fmaf(gscale, gv, a); };
+    const int njob = job.part ? job.C : 0;
+    const int F = job.in_chan + 3 + job.P;
+    if ((int)blockIdx.x < njob) {
+        const int c = blockIdx.x;
+        stem_combine_channel(job.part, job.nrec, job.spl, job.cp, job.P, job.C, c, s_r);
+        if ((int)threadIdx.x <= F) {
+            const bool bias = (int)threadIdx.x == F;
+            const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
+            const size_t i = bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x;
+            g[i] = gv;
+            add(acc[i], gv);
+        }
+        return;
+    }
+    const size_t jw0 = (size_t)job.w_off, jw1 = jw0 + (size_t)job.C * F, jb0 = (size_t)job.b_off, jb1 = jb0 + job.C;
+    auto mine = [&](size_t e) { return !(njob && ((e >= jw0 && e < jw1) || (e >= jb0 && e < jb1))); };
+    const size_t t0 = (size_t)(blockIdx.x - njob) * blockDim.x + threadIdx.x, nt = (size_t)(gridDim.x - njob) * blockDim.x;
+    if constexpr (VEC) {
+        const size_t n4 = n >> 2;
+        const size_t jlo = jw0 < jb0 ? jw0 : jb0, jhi = jw1 > jb1 ? jw1 : jb1;
+        for (size_t i = t0; i < n4; i += nt) {
+            if (njob && 4 * i < jhi && 4 * i + 4 > jlo) {  // a unit that touches the lifting layer's ranges: element by element
+                for (size_t e = 4 * i; e < 4 * i + 4; ++e)
+                    if (mine(e)) add(acc[e], g[e]);
+                continue;
+            }
+            const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i];
+            f32x4 ai;
+            if constexpr (INIT) ai = f32x4{0.f, 0.f, 0.f, 0.f};
+            else ai = reinterpret_cast<const f32x4*>(acc)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float aj = ai[j];
+                add(aj, gi[j]);
+                ai[j] = aj;
+            }
+            reinterpret_cast<f32x4*>(acc)[i] = ai;
+        }
+        for (size_t i = 4 * n4 + t0; i < n; i += nt)
+            if (mine(i)) add(acc[i], g[i]);
+    } else {
+        for (size_t i = t0; i < n; i += nt)
+            if (mine(i)) add(acc[i], g[i]);
+    }
+}
+
+int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,
+                         void* stream) {
+    CFD_REQUIRE(acc && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
+    if (n == 0) return CFD_OK;
+    const StemAdamJob jb = job ? *job : StemAdamJob{};
+    CFD_REQUIRE(!jb.part || (jb.P <= 8 && jb.in_chan + 3 + jb.P < 256), CFD_ERR_UNSUPPORTED, "cfd_fno_adam_step: lifting layer with %d case parameters", jb.P);
+    const bool vec = ((((uintptr_t)acc | (uintptr_t)grad) & 15) == 0) && n >= 4;
+    size_t blocks = ((vec ? n / 4 : n) + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    blocks += jb.part ? jb.C : 0;
+    CFD_PROF_W("k_grad_accum", (hipStream_t)stream, (init ? 8.0 : 12.0) * n, 2.0 * n);  // read g (and acc); write acc
+    const dim3 grid((unsigned)blocks), wg(256);
+    if (vec && init)
+        hipLaunchKernelGGL((k_grad_accum<true, true>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
+    else if (vec)
+        hipLaunchKernelGGL((k_grad_accum<true, false>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
+    else if (init)
+        hipLaunchKernelGGL((k_grad_accum<false, true>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
+    else
+        hipLaunchKernelGGL((k_grad_accum<false, false>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
+    CFD_LAUNCH_CHECK("cfd_fno_adam_step");
+    return CFD_OK;
+}
+
 // The same step for MANY parameter tensors in one launch (the autograd training paths of the U-Net / ResNet / DeepONet families keep
 // torch's per-tensor parameters: 136 / 28 / 33 tensors).  torch's fused multi-tensor Adam took 3 x 31 us for the U-Net's 4.4 MB and
 // 40 us for the Auto-DeepONet's 2.3 MB -- 7 % of that model's step.  The (p, g, m, v, n) table travels as the kernel argument;

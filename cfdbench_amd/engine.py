@@ -261,7 +261,11 @@ class FnoTrainEngine:
     deferred single-GPU step (``defer_flags``) it lacks the nMSE normaliser ``sums[3] / sums[2]`` (Adam's launch applies that factor)
     and its fc0 rows are written by the optimiser call itself; data-parallel, it is the SUM over ranks (Adam applies ``1 / world``);
     and it is never clipped.  Read gradients through ``gradients()`` (loss units, unclipped) and their norm through ``grad_norm()``;
-    calling ``torch.nn.utils.clip_grad_norm_`` on the engine's views clips the wrong numbers -- pass ``max_grad_norm`` instead."""
+    calling ``torch.nn.utils.clip_grad_norm_`` on the engine's views clips the wrong numbers -- pass ``max_grad_norm`` instead.
+
+    Gradient accumulation: ``accumulate(..., weight=1 / N, first=k == 0)`` for each of a group's N micro-batches, then
+    ``apply_accumulated()`` -- one optimiser step on ``sum_k weight_k * gradient_k``; ``train_step`` is the N = 1 case with its own,
+    shorter launch sequence and never touches the accumulator."""
 
     def __init__(self, model, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
@@ -321,6 +325,12 @@ class FnoTrainEngine:
                 raise ValueError("max_grad_norm must be > 0 (None: no clipping, float('inf'): measure the norm only)")
             self.clip = torch.zeros(CFD_CLIP_FLOATS, dtype=torch.float32, device=self.device)
             self.gstruct.clip, self.gstruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+        # gradient accumulation over micro-batches (accumulate / apply_accumulated): the accumulator, laid out like flat.grad, and its
+        # struct exist from the first accumulate() on -- an engine that never accumulates holds no more memory
+        self.accum: Optional[Tensor] = None
+        self.astruct = None
+        self._accum_open = False   # between an accumulate() and its apply_accumulated()
+        self._grad_in_accum = False  # whether the last optimiser step read the accumulator (gradients())
 
     # ------------------------------------------------------------------------------------------------
     def _prepare(self, inputs: Tensor, case_params: Tensor):
@@ -398,7 +408,60 @@ class FnoTrainEngine:
             handles.append(self.sync.reduce_slice_async(self.flat.grad, s0, s1))
         return self.sync.wait_all(handles)
 
+    def _no_open_group(self, what: str) -> None:
+        if self._accum_open:
+            raise RuntimeError(f"FnoTrainEngine.{what}: an accumulation group is open (accumulate() without its apply_accumulated()); "
+                               "the step would run on the last micro-batch's gradient alone")
+
+    # ---- gradient accumulation over micro-batches -----------------------------------------------------
+    def accumulate(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None, *, weight: float,
+                   first: bool) -> Tensor:
+        """One micro-batch of an accumulation group: forward + backward as in ``train_step`` (``defer_flags``; data-parallel: the
+        non-overlapped pass, nothing is exchanged here), then ``accumulator (+)= weight * gradient`` in the launch that is Adam's in a plain
+        step (cfd_fno_adam_step with CFD_STEP_ACCUMULATE: it finishes what the pass deferred, then adds instead of stepping).  ``first``
+        starts a group -- the accumulator is overwritten, never read; ``weight`` is usually 1 / (micro-batches of the group).  Returns the
+        device tensor of ``train_step`` for THIS micro-batch.  ``apply_accumulated()`` closes the group."""
+        from ._capi import CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE
+        if not first and not self._accum_open:
+            raise RuntimeError("FnoTrainEngine.accumulate: first=False without an open group (the accumulator holds nothing to add to)")
+        self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
+        if self.accum is None:
+            self.accum = torch.zeros_like(self.flat.grad)
+            base, g0 = self.accum.data_ptr(), self.flat.grad.data_ptr()
+            self.astruct = _param_struct([base + (p_ - g0) for p_ in self.flat.ptrs(True)], self.L)
+            if self.clip is not None:  # (read where the struct is the `grads` of the optimiser call on the accumulator)
+                self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+        flags = self.defer_flags | CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if first else 0)
+        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.astruct), ctypes.byref(self.gstruct),
+                      inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
+                      self.ws.data_ptr(), self.accum.data_ptr(), self.flat.grad.data_ptr(), None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0,
+                      0.0, 0, float(weight), self.loss_id, self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
+        self._last = (inputs, case_params, mask, 0)  # (the deferred work of this pass is done)
+        self._accum_open = True
+        return self.sums
+
+    def apply_accumulated(self) -> None:
+        """The optimiser step of an accumulation group: data-parallel, ONE all-reduce of the accumulator (DistributedDataParallel's
+        ``no_sync`` semantics: one exchange per optimiser step), then Adam -- with ``max_grad_norm`` the norm is taken of the accumulated
+        gradient -- as the plain optimiser call with the accumulator as its gradient buffer.  Afterwards ``gradients()`` returns the
+        accumulator (final, loss units, unclipped)."""
+        if not self._accum_open:
+            raise RuntimeError("FnoTrainEngine.apply_accumulated: nothing accumulated (call accumulate(..., first=True) first)")
+        scale = self.sync.all_reduce(self.accum)
+        self.step_count += 1
+        inputs, case_params, mask, _ = self._last
+        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.astruct),
+                      inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
+                      self.ws.data_ptr(), self.flat.data.data_ptr(), self.accum.data_ptr(), self.exp_avg.data_ptr(),
+                      self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                      self.step_count, scale, self.loss_id, self.act_dtype, 0, torch.cuda.current_stream().cuda_stream)
+        self._accum_open = False
+        self._grad_pending_scale = False
+        self._grad_in_accum = True
+
     def optimizer_step(self, grad_scale: float = 1.0):
+        self._no_open_group("optimizer_step")
+        self._grad_in_accum = False
         self.step_count += 1
         inputs, case_params, mask, flags = getattr(self, "_last", (None, None, None, 0))
         # the pass left work to this launch (nMSE normaliser from sums[2:4], the lifting layer's gradient rows), or the step clips: the
@@ -423,7 +486,10 @@ class FnoTrainEngine:
     def gradients(self) -> Tensor:
         """The flat gradient of the last step in the loss's own units, UNCLIPPED (with ``max_grad_norm`` Adam applied it times
         ``clip_coef()``; the buffer is never clipped).  After a deferred train_step (``defer_flags``) the buffer holds the gradients of
-        sum d^2 / n -- this returns them times n / sum (label*mask)^2; otherwise the buffer itself (data-parallel: the sum over ranks)."""
+        sum d^2 / n -- this returns them times n / sum (label*mask)^2; otherwise the buffer itself (data-parallel: the sum over ranks).
+        After ``apply_accumulated`` it is the accumulator: the weighted sum over the group's micro-batches, final."""
+        if self._grad_in_accum:
+            return self.accum
         if getattr(self, "_grad_pending_scale", False):
             return self.flat.grad * (self.sums[3] / self.sums[2])
         return self.flat.grad
@@ -443,6 +509,7 @@ class FnoTrainEngine:
     def train_step(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None) -> Tensor:
         """One optimisation step; returns the device tensor [sum sq err, sum abs err, sum sq label, n] of THIS rank's
         batch (no host sync -- read it with .tolist() only when logging)."""
+        self._no_open_group("train_step")
         if self.sync.exchange and self.overlap:
             scale = self.forward_backward_overlapped(inputs, label, case_params, mask)
         else:
@@ -499,6 +566,7 @@ class FnoTrainEngine:
         self._graph = g
 
     def train_step_graph(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+        self._no_open_group("train_step_graph")
         key = (*inputs.shape, case_params.shape[1], mask is not None)
         if self._graph is None or key != getattr(self, "_graph_key", None):  # a new batch shape needs a new capture
             self.capture(inputs, label, case_params, mask)

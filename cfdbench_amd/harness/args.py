@@ -18,7 +18,9 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``unroll_steps`` (train_auto, K > 1: the FNO is trained through a K-step rollout -- loss = mean nmse of K steps with every prediction
     fed back as the next input, cfdbench_amd/unroll.py; eager autograd path only; 1 = the reference's one-step loop),
     ``max_grad_norm`` (> 0: global gradient-norm clipping at that threshold before every optimiser step -- --fused 1: inside the engine's
-    optimiser call, eager paths: torch.nn.utils.clip_grad_norm_; 0.0 = off; not with --graph 1).
+    optimiser call, eager paths: torch.nn.utils.clip_grad_norm_; 0.0 = off; not with --graph 1),
+    ``fused_accumulation_steps`` (train_auto --fused 1, N > 1: N micro-batches per fused optimiser step -- FnoTrainEngine.accumulate /
+    apply_accumulated; what --gradient_accumulation_steps is to the autograd path; not with --graph 1).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -49,6 +51,7 @@ _FLAGS: Dict[str, Any] = dict(
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
+    fused_accumulation_steps=1,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -100,10 +103,15 @@ def is_args_valid(args: Args) -> None:
         assert args.model == "fno", "--dtype bf16 is built for the FNO (test_multistep, train_auto --fused 1)"
     if args.fused:
         assert args.model == "fno", "--fused 1 is the FnoTrainEngine path"
-        assert args.gradient_accumulation_steps == 1, "--fused 1 runs one fused optimiser step per batch"
+        assert args.gradient_accumulation_steps == 1, ("--fused 1 takes its micro-batches per optimiser step from "
+                                                       "--fused_accumulation_steps N, not from --gradient_accumulation_steps")
     if args.graph:
         assert not args.fused, "--graph 1 captures the autograd step; the fused FNO engine has its own launch path"
         assert args.gradient_accumulation_steps == 1, "--graph 1 captures one optimiser step per batch"
+    assert args.fused_accumulation_steps >= 1, "--fused_accumulation_steps counts the micro-batches of one fused optimiser step (1 = none)"
+    if args.fused_accumulation_steps > 1:
+        assert args.fused, "--fused_accumulation_steps > 1 is the fused FNO engine's option (--fused 1)"
+        assert not args.graph, "--fused_accumulation_steps > 1 with --graph 1 is not built"
     assert args.max_grad_norm >= 0.0, "--max_grad_norm is a threshold on the gradient's 2-norm (0 = no clipping)"
     if args.graph:
         assert not args.max_grad_norm > 0.0, "--graph 1 with --max_grad_norm is not built: the captured multi-tensor Adam has no clipping"

@@ -203,7 +203,10 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     Not with ``graph``.  The rank-0 log line then carries ``grad_norm`` (the norm before clipping, of the last optimiser step).
 
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
-    other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop."""
+    other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop.
+    ``gradient_accumulation_steps`` = N > 1 with ``fused``: FnoTrainEngine.accumulate per micro-batch (weight 1 / group) and
+    apply_accumulated at the group's boundary and at the epoch's last batch -- the eager path's grouping; one loss entry per micro-batch;
+    data-parallel, one gradient exchange per optimiser step.  Checkpoints fall on epoch ends, where no group is open."""
     rank, world = _rank_world()
     output_dir = Path(output_dir)
     clip = float(max_grad_norm) > 0.0
@@ -262,9 +265,6 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     if fused:
         if not isinstance(model, Fno2d):
             raise NotImplementedError("--fused 1 needs the fno model")
-        if accum > 1:
-            raise NotImplementedError("--gradient_accumulation_steps > 1 needs the autograd path (--fused 0): the engine's "
-                                      "backward pass overwrites the flat gradient")
         engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None)
         optimizer = None
     elif graph:
@@ -332,7 +332,14 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         for step, batch in enumerate(train_loader):
             if engine is not None:
                 engine.lr = cur_lr
-                sums = engine.train_step(batch["inputs"], batch["label"], batch["case_params"], batch["mask"])
+                if accum > 1:  # the eager path's grouping: the trailing group of an epoch may be shorter than `accum`
+                    group = accum if step < n_full else n_steps - n_full
+                    sums = engine.accumulate(batch["inputs"], batch["label"], batch["case_params"], batch["mask"], weight=1.0 / group,
+                                             first=step % accum == 0)
+                    if (step + 1) % accum == 0 or step + 1 == n_steps:
+                        engine.apply_accumulated()  # (data-parallel: the one gradient exchange of the group)
+                else:
+                    sums = engine.train_step(batch["inputs"], batch["label"], batch["case_params"], batch["mask"])
                 # nmse = sum sq err / sum sq label; kept on the device, fetched once per epoch (no per-step host sync)
                 ep_train_losses.append((sums[0] / sums[2]).clone())
                 loss_mse = loss_nmse = None
@@ -485,7 +492,8 @@ def main(argv=None):
               resume=bool(args.resume), device_loader=bool(args.device_loader), lr_scheduler_kind=args.lr_scheduler,
               lr_scheduler_factor=args.lr_scheduler_factor, lr_scheduler_patience=args.lr_scheduler_patience,
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
-              early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
+              early_stopping_delta=args.early_stopping_delta,
+              gradient_accumulation_steps=args.fused_accumulation_steps if args.fused else args.gradient_accumulation_steps,
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm)
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))

@@ -594,10 +594,29 @@ int cfd_fno_backward_phase_ex(const cfd_plan* plan, const cfd_fno_shape* shape, 
  * training keeps flags = 0: a rank's gradients must be final and normalised by ITS labels before they are all-reduced.
  * cfd_fno_adam_step: param / grad / exp_avg / exp_avg_sq = the flat buffers (n floats) that `params` / `grads` point into.  The backward
  * phases write every gradient TENSOR; elements of the flat buffers that belong to no tensor (alignment padding between tensors) are read
- * and updated like any other: the caller zeroes them once, nothing writes them afterwards.                                          */
+ * and updated like any other: the caller zeroes them once, nothing writes them afterwards.
+ *
+ * Gradient accumulation over micro-batches (FnoTrainEngine.accumulate / apply_accumulated) -- two more bits of cfd_fno_adam_step's `flags`,
+ * passed beside the CFD_TRAIN_DEFER_* bits of the pass; the forward call and the backward phases never see them:
+ *   CFD_STEP_ACCUMULATE    the call finishes this pass's gradient exactly as the optimiser call does -- s = grad_scale, times
+ *                          sums[3] / sums[2] where CFD_TRAIN_DEFER_SCALE applies (fp32, formed as for Adam); under CFD_TRAIN_DEFER_STEM the
+ *                          fc0 rows are finished from the workspace and stored into `grad` in the pass's unscaled units, so `grad` holds
+ *                          afterwards the bits the optimiser call would have left -- but its update rule is a sum instead of Adam:
+ *                              param[i] = fmaf(s, grad[i], param[i])           i < n
+ *                          `param` is an ACCUMULATOR of n floats laid out like `grad`, and `params` points into it at the offsets `grads`
+ *                          has into `grad`.  exp_avg, exp_avg_sq (may be NULL), lr, beta1, beta2, eps, weight_decay, step and grads->clip
+ *                          are not read: the norm is taken later, on the accumulator.
+ *   CFD_STEP_ACCUM_INIT    only together with CFD_STEP_ACCUMULATE (alone: CFD_ERR_INVALID_ARG): param[i] = s * grad[i]; the previous
+ *                          contents of the accumulator are never read (it may hold NaNs): the first micro-batch of a group.
+ * One thread writes each element, no atomics: two calls give the same bits.  12 bytes per element, 8 with CFD_STEP_ACCUM_INIT.  param or
+ * grad NULL: CFD_ERR_INVALID_ARG before any launch; n == 0: CFD_OK, nothing is launched.  The optimiser step on the accumulated gradient is
+ * the call WITHOUT these bits: flags = 0, grad = the accumulator, `grads` pointing into it (with `clip` set when clipping).  Without
+ * CFD_STEP_ACCUMULATE the call is what it was before the bits existed, bit for bit.                                                    */
 #define CFD_TRAIN_DEFER_SCALE 1
 #define CFD_TRAIN_DEFER_HEAD 2
 #define CFD_TRAIN_DEFER_STEM 4
+#define CFD_STEP_ACCUMULATE 8   /* cfd_fno_adam_step only */
+#define CFD_STEP_ACCUM_INIT 16  /* only together with CFD_STEP_ACCUMULATE */
 int cfd_fno_forward_train_f(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params,
                             const cfd_fno_params* grads, const float* inputs, const float* case_params, const float* mask,
                             const float* label, float* preds, float* sums, float* coef, void* ws, int which, float upstream,
