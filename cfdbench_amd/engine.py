@@ -425,12 +425,7 @@ class FnoTrainEngine:
         if not first and not self._accum_open:
             raise RuntimeError("FnoTrainEngine.accumulate: first=False without an open group (the accumulator holds nothing to add to)")
         self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
-        if self.accum is None:
-            self.accum = torch.zeros_like(self.flat.grad)
-            base, g0 = self.accum.data_ptr(), self.flat.grad.data_ptr()
-            self.astruct = _param_struct([base + (p_ - g0) for p_ in self.flat.ptrs(True)], self.L)
-            if self.clip is not None:  # (read where the struct is the `grads` of the optimiser call on the accumulator)
-                self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+        self._ensure_accum()
         flags = self.defer_flags | CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if first else 0)
         self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.astruct), ctypes.byref(self.gstruct),
                       inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
@@ -439,6 +434,126 @@ class FnoTrainEngine:
         self._last = (inputs, case_params, mask, 0)  # (the deferred work of this pass is done)
         self._accum_open = True
         return self.sums
+
+    def _ensure_accum(self) -> None:
+        if self.accum is None:
+            self.accum = torch.zeros_like(self.flat.grad)
+            base, g0 = self.accum.data_ptr(), self.flat.grad.data_ptr()
+            self.astruct = _param_struct([base + (p_ - g0) for p_ in self.flat.ptrs(True)], self.L)
+            if self.clip is not None:  # (read where the struct is the `grads` of the optimiser call on the accumulator)
+                self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+
+    # ---- training through a K-step rollout window ------------------------------------------------------
+    def _window_state(self, inputs: Tensor, case_params: Tensor, K: int, full: bool) -> dict:
+        """The buffers of a K-step window, per (shape key, K) as ``_prepare``'s are per shape: K prediction buffers and the (K, 4) sums;
+        for the full gradient also K training workspaces, K coefficient pairs, the two buffers that carry the chained gradient, and one
+        ``grads`` struct per step (they differ in ``d_inputs``)."""
+        self._prepare(inputs, case_params)
+        key = (self._shape_key, K)
+        if getattr(self, "_win_key", None) != key:
+            self._win = dict(preds=[torch.empty_like(self.preds) for _ in range(K)],
+                             sums=torch.zeros((K, 4), dtype=torch.float32, device=self.device))
+            self._win_key = key
+        w = self._win
+        if full and "ws" not in w:
+            w["ws"] = [torch.empty_like(self.ws) for _ in range(K)]
+            w["coef"] = torch.zeros((K, 2), dtype=torch.float32, device=self.device)
+            w["dx"] = [torch.empty_like(inputs) for _ in range(2)]
+            ptrs = self.flat.ptrs(True)
+            # step k (1-based) writes d loss / d x_k into dx[k % 2]; step 1 asks for none: the window's own inputs need no gradient
+            w["gs"] = [_param_struct(ptrs, self.L, d_inputs=w["dx"][k % 2].data_ptr() if k >= 2 else None) for k in range(1, K + 1)]
+        return w
+
+    def preds_seq(self) -> List[Tensor]:
+        """The K prediction buffers of the last window (K = 1: the one of the last pass); valid until the next window."""
+        if getattr(self, "_win_last", None) is None:
+            raise RuntimeError("FnoTrainEngine.preds_seq: no window has run")
+        return list(self._win_last)
+
+    def accumulate_window(self, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None, *,
+                          weight: float, first: bool, detach: bool = False) -> Tensor:
+        """One window of an accumulation group: ``accumulator (+)= weight * gradient of (1 / K) sum_k loss_k`` with ``x_1 = inputs`` and
+        prediction k fed back as the input of step k + 1 (``unroll.unrolled_loss``).  Returns the (K, 4) device tensor whose row k is
+        ``train_step``'s ``[sum sq err, sum abs err, sum sq label, n]`` of step k; ``preds_seq()`` the K predictions.  Group rules as
+        ``accumulate``'s; ``apply_accumulated()`` closes the group, so clipping takes the norm of the whole window's (group's) gradient
+        and a data-parallel run exchanges the accumulator once per optimiser step.
+
+        ``detach=False``: the full gradient, through every fed-back frame.  K forward passes (flags = 0), each on a workspace of its own,
+        then the backward passes K .. 1: step k's gradient of its inputs (``grads->d_inputs``) is step k - 1's external gradient on its
+        predictions (``gpreds_ext``), and behind each pass the accumulate call adds ``weight`` times its parameter gradient.  The 1 / K
+        rides in the loss coefficients (``upstream``).  fp32 activation storage only.
+        ``detach=True`` (the pushforward trick): the fed-back frame is a constant, so the window is K plain micro-batches of weight
+        ``weight / K`` -- ``accumulate`` itself, with deferred launches, one-pass head and bf16 storage as there."""
+        from ._capi import CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE
+        K = len(labels_seq)
+        if K < 1:
+            raise ValueError("FnoTrainEngine.accumulate_window: no label frames")
+        if inputs.shape[1] != self.cfg["out_chan"] or labels_seq[0].shape[1] != inputs.shape[1]:
+            raise ValueError(f"FnoTrainEngine.accumulate_window: the predictions are fed back as inputs, so in_chan == out_chan is required "
+                             f"(inputs have {inputs.shape[1]} channels, the model predicts {self.cfg['out_chan']})")
+        if K >= 2 and not detach and self.act_dtype:
+            raise ValueError("FnoTrainEngine.accumulate_window: the full gradient through the fed-back frames needs fp32 activation storage "
+                             "(the input gradient of a bf16-storage pass is not built); use detach=True or act_dtype='fp32'")
+        if not first and not self._accum_open:
+            raise RuntimeError("FnoTrainEngine.accumulate_window: first=False without an open group (the accumulator holds nothing to add to)")
+        if K == 1:
+            sums = self.accumulate(inputs, labels_seq[0], case_params, mask, weight=weight, first=first)
+            self._win_last = [self.preds]
+            return sums.view(1, 4)
+        w = self._window_state(inputs, case_params, K, full=not detach)
+        if detach:
+            own = (self.preds, self.sums)
+            try:
+                x = inputs
+                for k in range(K):  # step k + 1 reads preds_k while it writes preds_{k+1}: every step has its own buffer (and sums row)
+                    self.preds, self.sums = w["preds"][k], w["sums"][k]
+                    self.accumulate(x, labels_seq[k], case_params, mask, weight=weight / K, first=first and k == 0)
+                    x = w["preds"][k]
+            finally:
+                self.preds, self.sums = own
+            self._win_last = w["preds"]
+            return w["sums"]
+        a, st = self.api, torch.cuda.current_stream().cuda_stream
+        for t in (inputs, case_params, mask, *labels_seq):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
+        self._ensure_accum()
+        plan, sh, pr = self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct)
+        cp, mk = case_params.data_ptr(), None if mask is None else mask.data_ptr()
+        xs = [inputs] + w["preds"][:-1]
+        one_pass = [False] * K
+
+        def args(k):  # (grads struct, the five data pointers, sums, coef, workspace) of step k (0-based)
+            return (ctypes.byref(w["gs"][k]), (xs[k].data_ptr(), cp, mk, labels_seq[k].data_ptr(), w["preds"][k].data_ptr()),
+                    w["sums"][k].data_ptr(), w["coef"][k].data_ptr(), w["ws"][k].data_ptr())
+
+        for k in range(K):
+            gr, data, sums, coef, ws = args(k)
+            if k == K - 1 and self.fused_head:  # no chained gradient on the last step: the head runs once for both directions
+                a.call("cfd_fno_forward_train_f", plan, sh, pr, gr, *data, sums, coef, ws, self.loss_id, 1.0 / K, 0, 0, st)
+                one_pass[k] = True
+            else:
+                a.call("cfd_fno_forward", plan, sh, pr, *data, sums, ws, 1, st)
+                a.call("cfd_loss_coef", sums, coef, self.loss_id, 1.0 / K, st)
+        for k in range(K - 1, -1, -1):
+            gr, data, sums, coef, ws = args(k)
+            gext = w["dx"][k % 2].data_ptr() if k < K - 1 else None  # = d_inputs of step k + 1 (1-based k + 2: dx[(k + 2) % 2])
+            for phase in range(1 if one_pass[k] else 0, self.L + 2):
+                a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *data, gext, coef, sums, ws, phase, self.loss_id, 0, 0, st)
+            flags = CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if (first and k == K - 1) else 0)
+            a.call("cfd_fno_adam_step", plan, sh, ctypes.byref(self.astruct), gr, data[0], cp, mk, sums, ws, self.accum.data_ptr(),
+                   self.flat.grad.data_ptr(), None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 0, float(weight), self.loss_id, 0, flags, st)
+        self._last = (inputs, case_params, mask, 0)
+        self._accum_open = True
+        self._win_last = w["preds"]
+        return w["sums"]
+
+    def train_window(self, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None,
+                     detach: bool = False) -> Tensor:
+        """One optimisation step on a K-step window: ``accumulate_window(weight=1.0, first=True)`` + ``apply_accumulated()``."""
+        sums = self.accumulate_window(inputs, labels_seq, case_params, mask, weight=1.0, first=True, detach=detach)
+        self.apply_accumulated()
+        return sums
 
     def apply_accumulated(self) -> None:
         """The optimiser step of an accumulation group: data-parallel, ONE all-reduce of the accumulator (DistributedDataParallel's

@@ -16,7 +16,11 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``dtype`` ("bf16": the FNO's activations between kernels are stored as bf16 -- test_multistep: BASELINE configs[4];
     train_auto --fused 1: bf16-storage training with fp32 master weights, gradients and optimiser),
     ``unroll_steps`` (train_auto, K > 1: the FNO is trained through a K-step rollout -- loss = mean nmse of K steps with every prediction
-    fed back as the next input, cfdbench_amd/unroll.py; eager autograd path only; 1 = the reference's one-step loop),
+    fed back as the next input, cfdbench_amd/unroll.py; 1 = the reference's one-step loop.  On the autograd path, or with --fused 1 as
+    FnoTrainEngine windows; with --device_loader 1 on both; with --fused_accumulation_steps N: N windows per optimiser step.  Not with
+    --graph 1, not with a model other than the FNO, and with --dtype bf16 only together with --unroll_detach 1),
+    ``unroll_detach`` (1: the fed-back frame of a window carries no gradient -- the pushforward trick; the gradient is the mean of K
+    one-step gradients taken along the model's own rollout; 0 = the full gradient through every fed-back frame),
     ``max_grad_norm`` (> 0: global gradient-norm clipping at that threshold before every optimiser step -- --fused 1: inside the engine's
     optimiser call, eager paths: torch.nn.utils.clip_grad_norm_; 0.0 = off; not with --graph 1),
     ``fused_accumulation_steps`` (train_auto --fused 1, N > 1: N micro-batches per fused optimiser step -- FnoTrainEngine.accumulate /
@@ -51,7 +55,7 @@ _FLAGS: Dict[str, Any] = dict(
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
-    fused_accumulation_steps=1,
+    fused_accumulation_steps=1, unroll_detach=0,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -116,6 +120,17 @@ def is_args_valid(args: Args) -> None:
     if args.graph:
         assert not args.max_grad_norm > 0.0, "--graph 1 with --max_grad_norm is not built: the captured multi-tensor Adam has no clipping"
     assert args.unroll_steps >= 1, "--unroll_steps counts the model steps of one training window (1 = the one-step loop)"
+    assert args.unroll_detach in (0, 1), "--unroll_detach is 0 (full gradient through the fed-back frames) or 1 (none)"
+    if args.unroll_steps > 1:
+        assert args.model == "fno", ("--unroll_steps > 1 needs the fno model: the one model whose step hands back the gradient of its "
+                                     "inputs")
+        assert not args.graph, "--unroll_steps > 1 with --graph 1 is not built: the captured step is the one-step loop"
+        assert args.dtype == "fp32" or args.unroll_detach, ("--dtype bf16 --unroll_steps > 1 needs --unroll_detach 1: the input gradient "
+                                                           "of a bf16-storage pass is not built")
+        if not args.fused:
+            assert args.gradient_accumulation_steps == 1, "--unroll_steps > 1 on the autograd path needs gradient_accumulation_steps == 1"
+    else:
+        assert not args.unroll_detach, "--unroll_detach 1 is an option of --unroll_steps > 1"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

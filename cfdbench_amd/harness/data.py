@@ -93,11 +93,21 @@ class DeviceBatchLoader:
 
     ``data`` needs the attributes of the reference's datasets: ``inputs``, ``labels``, ``case_ids``, ``case_params``.
     ``indices`` restricts the loader to a subset (data-parallel shard).  The permutation is drawn from the host generator
-    (``torch.randperm``), so seeding / ``--resume`` behave as with a DataLoader."""
+    (``torch.randperm``), so seeding / ``--resume`` behave as with a DataLoader.
+
+    ``window_labels`` (training through a rollout, cfdbench_amd/unroll.py): the ``(n_windows, K)`` ``label_idx`` of ``unroll_windows``.
+    The loader's items are then WINDOW numbers (``indices`` restricts those), a batch is gathered from the windows' start items
+    (column 0) and carries ``labels_seq`` as well: K label tensors, ``labels_seq[0]`` being ``label`` itself and ``labels_seq[k]`` the
+    label frames of the items in column k -- the dict ``unroll.collate_windows`` builds, K - 1 gathers more per batch."""
 
     def __init__(self, data, batch_size: int, shuffle: bool = True, drop_last: bool = False, device: str = "cuda",
-                 indices=None, generator=None):
+                 indices=None, generator=None, window_labels: Optional[torch.Tensor] = None):
         self.batch_size, self.shuffle, self.drop_last, self.generator = int(batch_size), shuffle, drop_last, generator
+        self.window_labels = None
+        if window_labels is not None:
+            if window_labels.dim() != 2 or window_labels.shape[1] < 1:
+                raise ValueError("DeviceBatchLoader: window_labels must be the (n_windows, K) label_idx of unroll_windows")
+            self.window_labels = window_labels.to(dtype=torch.long, device=device)
         # resident planes, split the way a batch is consumed: fields (N, c, h, w), mask (N, 1, h, w), next frame's fields (N, c, h, w).
         # (Round 6: one gather per batch tensor and no `.contiguous()` of channel slices -- three copy launches less per batch; the labels'
         # mask channel, which no consumer reads, is not kept.)
@@ -113,7 +123,7 @@ class DeviceBatchLoader:
     def set_indices(self, indices=None) -> None:
         """Restrict the loader to ``indices`` (None = every frame) WITHOUT touching the resident tensors: a data-parallel run
         re-partitions the frames every epoch, and only this index list changes -- the corpus is uploaded once."""
-        n = len(self.inputs)
+        n = len(self.inputs) if self.window_labels is None else len(self.window_labels)  # (items: frames, or windows)
         self.indices = torch.arange(n) if indices is None else torch.as_tensor(indices, dtype=torch.long)
 
     def __len__(self) -> int:
@@ -127,6 +137,13 @@ class DeviceBatchLoader:
         order = order.to(self.inputs.device)
         for k in range(len(self)):
             idx = order[k * self.batch_size:(k + 1) * self.batch_size]
+            if self.window_labels is not None:
+                rows = self.window_labels.index_select(0, idx)
+                batch = {name: t.index_select(0, rows[:, 0]) for name, t in
+                         dict(inputs=self.inputs, label=self.labels, mask=self.mask, case_params=self.case_params).items()}
+                batch["labels_seq"] = [batch["label"]] + [self.labels.index_select(0, rows[:, j]) for j in range(1, rows.shape[1])]
+                yield batch
+                continue
             src = dict(inputs=self.inputs, label=self.labels, mask=self.mask, case_params=self.case_params)
             out = self._bound
             if out is not None and len(idx) == out["inputs"].shape[0]:
@@ -142,6 +159,9 @@ class DeviceBatchLoader:
         """Gather every full-size batch into ``buffers`` (a dict with inputs / label / mask / case_params tensors of one batch's shapes and
         this loader's device, e.g. ``GraphedTrainStep.static``) instead of fresh tensors; ``None`` unbinds.  The yielded dict then holds
         those very tensors -- valid until the next batch is drawn."""
+        if self.window_labels is not None:
+            raise ValueError("DeviceBatchLoader.bind: a loader of rollout windows (window_labels) has no bound buffers -- the captured "
+                             "step is the one-step loop and reads one label frame")
         if buffers is not None:
             for name, ref in dict(inputs=self.inputs, label=self.labels, mask=self.mask, case_params=self.case_params).items():
                 b = buffers.get(name)

@@ -91,12 +91,15 @@ def average_buffers(model: torch.nn.Module) -> None:
             b.data.mul_(1.0 / world)
 
 
-def check_resume_state(state: dict, fused: bool, world: int, unroll_steps: int = 1) -> None:
+def check_resume_state(state: dict, fused: bool, world: int, unroll_steps: int = 1, unroll_detach: int = 0) -> None:
     """A saved training state continues only the kind of run that wrote it (optimizer layout and shard sizes differ; an unrolled run
     shares its result directory with the one-step run of the same arguments and trains on another loss)."""
     if int(state.get("unroll_steps", 1)) != int(unroll_steps):
         raise RuntimeError(f"train_state.pt was written with --unroll_steps {int(state.get('unroll_steps', 1))}, this run uses "
                            f"--unroll_steps {int(unroll_steps)}")
+    if int(state.get("unroll_detach", 0)) != int(unroll_detach):  # (a state without the key: written before the flag existed, i.e. 0)
+        raise RuntimeError(f"train_state.pt was written with --unroll_detach {int(state.get('unroll_detach', 0))}, this run uses "
+                           f"--unroll_detach {int(unroll_detach)}: the two train on different gradients")
     if "fused" in state and bool(state["fused"]) != bool(fused):
         raise RuntimeError(f"train_state.pt was written with --fused {int(state['fused'])}, this run uses --fused {int(fused)}")
     if "world" in state and int(state["world"]) != int(world):

@@ -7,6 +7,7 @@ Two training paths:
     (train_auto.py:231-257) on the drop-in ``Fno2d`` (one autograd node over the HIP kernels);
   * ``--fused 1`` -- ``FnoTrainEngine``: forward + nMSE + backward + flat Adam as C-ABI calls without autograd and
     without the per-step ``.item()`` host sync (scores are read every ``log_interval`` steps only).
+``--unroll_steps K`` trains either path through a K-step rollout window (``unroll.unrolled_loss`` / ``FnoTrainEngine.train_window``).
 Both use Adam(lr) + StepLR(lr_step_size, gamma) per epoch and write the same files: ckpt-{ep}/{model.pt,
 dev_scores.json, train_loss.json, scores.json}, train_losses.json, test/{preds.pt, scores.json}, args.json.
 Under torch.distributed (one process per GPU) each rank trains on its shard of the frames, gradients are summed over
@@ -178,7 +179,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           plot_interval: int = 1, resume: bool = False, device_loader: bool = False, lr_scheduler_kind: str = "step",
           lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5, early_stopping_patience: int = 0,
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
-          unroll_steps: int = 1, max_grad_norm: float = 0.0):
+          unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     ``graph`` (autograd path; with several ranks the gradient exchange sits between two graphs, cfdbench_amd/graph.py): the step ``model(**batch) -> loss["nmse"].backward() -> Adam.step()`` is captured once
@@ -193,9 +194,13 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     state); with ``resume`` a run that finds it reloads the weights of that checkpoint and continues with the NEXT epoch,
     reproducing the uninterrupted run step for step (same shuffles, same Adam state).
 
-    ``unroll_steps`` = K > 1 (the FNO on the eager autograd path only): a training item is a window of K consecutive frames of one case
-    and the loss the mean nmse of K model steps with every prediction fed back as the next input (cfdbench_amd/unroll.py); the gradient
-    flows through the fed-back frames.  Evaluation, checkpoints and the result tree are those of K = 1.
+    ``unroll_steps`` = K > 1 (the FNO): a training item is a window of K consecutive frames of one case and the loss the mean nmse of K
+    model steps with every prediction fed back as the next input (cfdbench_amd/unroll.py); the gradient flows through the fed-back
+    frames unless ``unroll_detach`` (the pushforward trick: the fed-back frame is a constant).  Eager: ``unrolled_loss``; ``fused``:
+    ``FnoTrainEngine.train_window``, or with ``gradient_accumulation_steps`` = N > 1 ``accumulate_window`` (weight 1 / group) per
+    window and ``apply_accumulated`` per group; ``device_loader``: the windows are gathered on the device.  The logged training loss is
+    the mean over the K steps' nmse.  Not with ``graph``; bf16 storage only with ``unroll_detach``.  Evaluation, checkpoints and the
+    result tree are those of K = 1.
 
     ``max_grad_norm`` > 0: global gradient-norm clipping (2-norm over all parameters) before every optimiser step.  ``fused``: inside
     the engine's optimiser call, where its gradient becomes final (FnoTrainEngine(max_grad_norm=)); the eager paths (any model,
@@ -215,21 +220,28 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     if clip and graph:
         raise NotImplementedError("--max_grad_norm needs --graph 0: the captured multi-tensor Adam step has no clipping")
     unroll = int(unroll_steps)
+    detach = bool(unroll_detach)
+    if detach and unroll <= 1:
+        raise ValueError("--unroll_detach 1 is an option of --unroll_steps > 1")
     windows = None
     if unroll > 1:
         if not isinstance(model, Fno2d):
             raise NotImplementedError("--unroll_steps > 1 needs the fno model: the one model that hands autograd its input gradient "
                                       "through one node")
-        if fused:
-            raise NotImplementedError("--unroll_steps > 1 needs the autograd path (--fused 0): the engine's weight-gradient kernels "
-                                      "overwrite the flat gradient and cannot accumulate over the steps of a window")
         if graph:
             raise NotImplementedError("--unroll_steps > 1 runs eagerly (--graph 0): the captured step is the one-step loop")
-        if device_loader:
-            raise NotImplementedError("--unroll_steps > 1 needs the DataLoader path (--device_loader 0): the resident loader gathers "
-                                      "one label frame per item")
-        if max(1, int(gradient_accumulation_steps)) > 1:
-            raise NotImplementedError("--unroll_steps > 1 needs gradient_accumulation_steps == 1")
+        on_gpu = any(p_.is_cuda for p_ in model.parameters())
+        if fused and not on_gpu:
+            raise NotImplementedError("--unroll_steps > 1 with --fused 1 runs FnoTrainEngine windows, which need the model on the GPU "
+                                      "(no CPU fallback)")
+        if device_loader and not on_gpu:
+            raise NotImplementedError("--unroll_steps > 1 with --device_loader 1 gathers the windows on the GPU and needs the model there")
+        if not fused and max(1, int(gradient_accumulation_steps)) > 1:
+            raise NotImplementedError("--unroll_steps > 1 on the autograd path needs gradient_accumulation_steps == 1 (the fused engine "
+                                      "accumulates windows: --fused 1 --fused_accumulation_steps N)")
+        if fused and act_dtype not in ("fp32", "f32", "float32") and not detach:
+            raise NotImplementedError("--dtype bf16 --unroll_steps > 1 needs --unroll_detach 1: the input gradient of a bf16-storage "
+                                      "pass is not built")
         windows = unroll_windows(train_data, unroll)
         if not windows[0]:
             raise ValueError(f"--unroll_steps {unroll}: no case of the training split has that many consecutive frames")
@@ -242,6 +254,14 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         rank does not see the same 1/world of the data for the whole run."""
         n_items = len(train_data) if windows is None else len(windows[0])
         shard = shard_indices(n_items, rank, world, batch_size, epoch=ep) if world > 1 else None
+        if windows is not None and device_loader:  # the same batches, gathered on the device (window numbers are the loader's items)
+            from .data import DeviceBatchLoader
+            if resident:
+                resident[0].set_indices(shard)
+            else:
+                resident.append(DeviceBatchLoader(train_data, batch_size, shuffle=True, drop_last=world > 1, indices=shard,
+                                                  window_labels=windows[1]))
+            return resident[0]
         if windows is not None:  # items = window numbers; the batch carries the K label frames (unroll.collate_windows)
             items = list(range(n_items)) if shard is None else [int(i) for i in shard]
             return DataLoader(items, batch_size=batch_size, shuffle=True, drop_last=world > 1,
@@ -294,7 +314,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     state_path = output_dir / "train_state.pt"
     if resume and state_path.exists():
         state = torch.load(state_path, map_location="cpu", weights_only=False)
-        check_resume_state(state, fused=engine is not None, world=world, unroll_steps=unroll)
+        check_resume_state(state, fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach))
         model.load_state_dict(torch.load(output_dir / state["ckpt"] / "model.pt", map_location="cpu"))
         if hasattr(model, "load_extra_train_state") and state.get("model_extra") is not None:
             model.load_extra_train_state(state["model_extra"])  # e.g. ResNet's dropout step counter
@@ -332,7 +352,13 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         for step, batch in enumerate(train_loader):
             if engine is not None:
                 engine.lr = cur_lr
-                if accum > 1:  # the eager path's grouping: the trailing group of an epoch may be shorter than `accum`
+                if windows is not None:  # a window per batch; with accumulation `accum` windows per optimiser step
+                    group = accum if step < n_full else n_steps - n_full
+                    wsums = engine.accumulate_window(batch["inputs"], batch["labels_seq"], batch["case_params"], batch["mask"],
+                                                     weight=1.0 / group, first=step % accum == 0, detach=detach)
+                    if (step + 1) % accum == 0 or step + 1 == n_steps:
+                        engine.apply_accumulated()
+                elif accum > 1:  # the eager path's grouping: the trailing group of an epoch may be shorter than `accum`
                     group = accum if step < n_full else n_steps - n_full
                     sums = engine.accumulate(batch["inputs"], batch["label"], batch["case_params"], batch["mask"], weight=1.0 / group,
                                              first=step % accum == 0)
@@ -341,7 +367,10 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 else:
                     sums = engine.train_step(batch["inputs"], batch["label"], batch["case_params"], batch["mask"])
                 # nmse = sum sq err / sum sq label; kept on the device, fetched once per epoch (no per-step host sync)
-                ep_train_losses.append((sums[0] / sums[2]).clone())
+                if windows is not None:  # the mean over the window's steps, from the (K, 4) tensor -- on the device like the rest
+                    ep_train_losses.append((wsums[:, 0] / wsums[:, 2]).mean())
+                else:
+                    ep_train_losses.append((sums[0] / sums[2]).clone())
                 loss_mse = loss_nmse = None
             elif graph:
                 from ..graph import GraphedTrainStep
@@ -369,7 +398,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 loss_mse, loss_nmse = loss["mse"], loss["nmse"]
             else:
                 if windows is not None:
-                    nmse, preds_seq = unrolled_loss(model, batch["inputs"], batch["labels_seq"], batch["case_params"], batch["mask"])
+                    nmse, preds_seq = unrolled_loss(model, batch["inputs"], batch["labels_seq"], batch["case_params"], batch["mask"],
+                                                    detach=detach)
                     with torch.no_grad():  # (the log line's mse: the last step's)
                         mse = ((preds_seq[-1] - batch["labels_seq"][-1] * batch["mask"]) ** 2).mean()
                     outputs = dict(preds=preds_seq[0], loss=dict(nmse=nmse, mse=mse))
@@ -392,7 +422,10 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 loss_mse, loss_nmse = loss["mse"], loss["nmse"]
             global_step += 1
             if global_step % log_interval == 0 and rank == 0:
-                if engine is not None:
+                if engine is not None and windows is not None:  # (the log line's mse: the last step's, as on the eager path)
+                    rows = wsums.tolist()
+                    mse_v, nmse_v = rows[-1][0] / rows[-1][3], float(np.mean([r_[0] / r_[2] for r_ in rows]))
+                elif engine is not None:
                     sc = engine.scores()
                     mse_v, nmse_v = sc["mse"], sc["nmse"]
                 else:
@@ -440,7 +473,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             tmp = output_dir / "train_state.pt.tmp"
             torch.save(dict(format=2, ep=ep, global_step=global_step, train_losses=train_losses, ckpt=ckpt_dir.name,
                             optimizer=opt_state, scheduler=schedule.state_dict(), early_stopping=stopper.state_dict(),
-                            rng=torch.get_rng_state(), fused=engine is not None, world=world, unroll_steps=unroll,
+                            rng=torch.get_rng_state(), fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach),
                             model_extra=model.extra_train_state() if hasattr(model, "extra_train_state") else None), tmp)
             tmp.replace(state_path)
         else:
@@ -494,7 +527,8 @@ def main(argv=None):
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta,
               gradient_accumulation_steps=args.fused_accumulation_steps if args.fused else args.gradient_accumulation_steps,
-              act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm)
+              act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
+              unroll_detach=bool(args.unroll_detach))
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

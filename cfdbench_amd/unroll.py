@@ -27,9 +27,13 @@ def unroll_windows(dataset, K: int) -> Tuple[List[int], Tensor]:
     return starts, label_idx
 
 
-def unrolled_loss(model, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None):
+def unrolled_loss(model, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None,
+                  detach: bool = False):
     """``preds_1 = model(inputs)``, ``preds_k = model(preds_{k-1})``; returns ``(loss, preds)`` with ``loss = (1/K) sum_k nmse_k`` against
-    ``labels_seq[k - 1]`` and ``preds`` the K predictions.  ``loss.backward()`` reaches the parameters through every fed-back frame."""
+    ``labels_seq[k - 1]`` and ``preds`` the K predictions.  ``loss.backward()`` reaches the parameters through every fed-back frame.
+
+    ``detach`` (the pushforward trick): the fed-back frame is ``preds.detach()`` -- step k + 1 trains on the model's own prediction as a
+    constant input, so the gradient is the sum of K one-step gradients and nothing flows through the frames."""
     K = len(labels_seq)
     if K < 1:
         raise ValueError("unrolled_loss: no label frames")
@@ -39,8 +43,8 @@ def unrolled_loss(model, inputs: Tensor, labels_seq: Sequence[Tensor], case_para
     x, preds, loss = inputs, [], None
     for label in labels_seq:
         out = model(inputs=x, case_params=case_params, mask=mask, label=label)
-        x = out["preds"]
-        preds.append(x)
+        preds.append(out["preds"])
+        x = out["preds"].detach() if detach else out["preds"]
         loss = out["loss"]["nmse"] if loss is None else loss + out["loss"]["nmse"]
     return loss / K, preds
 
