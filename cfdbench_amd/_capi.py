@@ -15,6 +15,7 @@ CFD_CLIP_FLOATS = 1024  # floats of cfd_fno_params.clip (include/cfdbench_amd.h)
 # bits of cfd_fno_adam_step's `flags` beside CFD_TRAIN_DEFER_* (1, 2, 4): gradient accumulation over micro-batches
 CFD_STEP_ACCUMULATE = 8   # param = an accumulator laid out like grad: param[i] = fmaf(s, grad[i], param[i]) instead of Adam
 CFD_STEP_ACCUM_INIT = 16  # with CFD_STEP_ACCUMULATE: param[i] = s * grad[i], the previous contents are never read
+CFD_STEP_DECOUPLED_WD = 32  # AdamW: param[i] *= 1 - lr * weight_decay, then Adam on the undecayed gradient (ignored with CFD_STEP_ACCUMULATE)
 
 
 class CfdError(RuntimeError):

@@ -492,5 +492,6 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
         return cfd_int_grad_accum_f(param, grad, n, grad_scale, rt.scale ? sums : nullptr, rt.stem ? &job : nullptr,
                                     (flags & CFD_STEP_ACCUM_INIT) != 0, stream);
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                               rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm, stream);
+                               rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm,
+                               (flags & CFD_STEP_DECOUPLED_WD) != 0, stream);
 }

@@ -1715,10 +1715,21 @@ extern "C" int cfd_gelu_bwd(const float* x, const float* gy, float* gx, size_t n
 // ------------------------------------------------------------------------------------------------------
 // Adam  (torch.optim.Adam defaults: amsgrad=False, maximize=False; train_auto.py:213)
 // ------------------------------------------------------------------------------------------------------
+// DW (CFD_STEP_DECOUPLED_WD of cfd_fno_adam_step; torch.optim.AdamW's single-tensor path): `wd` carries the factor 1 - lr * weight_decay
+// (formed on the host in double, rounded to fp32) and the parameter is multiplied by it before the update; the gradient stays undecayed.
+// The product and the scaled gradient are made opaque so that each is rounded on its own and what follows contracts exactly as it does
+// without DW: a factor of 1 (weight_decay = 0) then gives the bits of plain Adam, with any gradient scale.  The instantiations without DW
+// are the code they were before DW existed.
+template <bool DW = false>
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
                                             float bc1, float rsqrt_bc2, float gscale) {
     float gi = g * gscale;
-    if (wd != 0.f) gi = fmaf(wd, p, gi);
+    if constexpr (DW) {
+        gi = cfd_opaque_f(gi);  // (rounded on its own, as the select on wd below leaves it: not contracted into gi - m)
+        p = cfd_opaque_f(p * wd);
+    } else {
+        if (wd != 0.f) gi = fmaf(wd, p, gi);
+    }
     m = fmaf(1.f - b1, gi - m, m);                 // m.lerp_(g, 1-b1)
     v = fmaf(b2, v, (1.f - b2) * gi * gi);         // v.mul_(b2).addcmul_(g, g, 1-b2)
     const float denom = sqrtf(v) * rsqrt_bc2 + eps;  // sqrt(v)/sqrt(bc2) + eps
@@ -1851,7 +1862,9 @@ __global__ __launch_bounds__(256) void k_gradsq(float* __restrict__ g, size_t n,
 // factor n / sum (label*mask)^2 = sums[3] / sums[2] (both left by the head's reduction; k_label_energy_part + _coef: two launches, 10 us);
 // (b) the lifting layer's gradient: workgroup c < job.C finishes row c of fc0 from the sum records of k_block<.., STEMG>, stores it (in
 // the same, still unscaled units as every other gradient) and applies Adam to it; the flat part skips those two ranges.
-template <bool VEC>
+// DW: decoupled weight decay (adam_update<true>: the `wd` argument is the factor 1 - lr * weight_decay); a variant of its own, so the
+// code of k_adam_f<VEC, false> is what k_adam_f<VEC> was.
+template <bool VEC, bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
                                                 float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip) {
@@ -1875,7 +1888,7 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
             const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
             const size_t i = bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x;
             g[i] = gv;
-            adam_update(p[i], gv, m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+            adam_update<DW>(p[i], gv, m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
         }
         return;
     }
@@ -1888,7 +1901,7 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
         for (size_t i = t0; i < n4; i += nt) {
             if (njob && 4 * i < jhi && 4 * i + 4 > jlo) {  // a unit that touches the lifting layer's ranges: element by element
                 for (size_t e = 4 * i; e < 4 * i + 4; ++e)
-                    if (mine(e)) adam_update(p[e], g[e], m[e], v[e], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+                    if (mine(e)) adam_update<DW>(p[e], g[e], m[e], v[e], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
                 continue;
             }
             f32x4 pi = reinterpret_cast<const f32x4*>(p)[i], mi = reinterpret_cast<const f32x4*>(m)[i], vi = reinterpret_cast<const f32x4*>(v)[i];
@@ -1896,7 +1909,7 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float pj = pi[j], mj = mi[j], vj = vi[j];
-                adam_update(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+                adam_update<DW>(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
                 pi[j] = pj, mi[j] = mj, vi[j] = vj;
             }
             reinterpret_cast<f32x4*>(m)[i] = mi;
@@ -1904,16 +1917,16 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
             reinterpret_cast<f32x4*>(p)[i] = pi;
         }
         for (size_t i = 4 * n4 + t0; i < n; i += nt)
-            if (mine(i)) adam_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+            if (mine(i)) adam_update<DW>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
     } else {
         for (size_t i = t0; i < n; i += nt)
-            if (mine(i)) adam_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+            if (mine(i)) adam_update<DW>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
     }
 }
 
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, void* stream) {
+                        float max_grad_norm, int decoupled, void* stream) {
     CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: step must be >= 1");
     CFD_REQUIRE(!clip || max_grad_norm > 0.f, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: max_grad_norm must be > 0 (+inf: measure only)");
@@ -1944,12 +1957,22 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
     }
     blocks += jb.part ? jb.C : 0;
     CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
-    if (vec)
-        hipLaunchKernelGGL(k_adam_f<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb, ca);
+    const dim3 grid((unsigned)blocks), wg(256);
+    const float rbc1 = (float)bc1, rbc2 = (float)(1.0 / sqrt(bc2));
+    if (decoupled) {  // AdamW: p *= 1 - lr * wd (the factor in double, rounded once, as torch forms it), then Adam on the undecayed gradient
+        const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
+        if (vec)
+            hipLaunchKernelGGL((k_adam_f<true, true>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                               decay, rbc1, rbc2, grad_scale, sums, jb, ca);
+        else
+            hipLaunchKernelGGL((k_adam_f<false, true>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                               decay, rbc1, rbc2, grad_scale, sums, jb, ca);
+    } else if (vec)
+        hipLaunchKernelGGL((k_adam_f<true, false>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                           weight_decay, rbc1, rbc2, grad_scale, sums, jb, ca);
     else
-        hipLaunchKernelGGL(k_adam_f<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, sums, jb, ca);
+        hipLaunchKernelGGL((k_adam_f<false, false>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                           weight_decay, rbc1, rbc2, grad_scale, sums, jb, ca);
     CFD_LAUNCH_CHECK("cfd_fno_adam_step");
     return CFD_OK;
 }

@@ -5,6 +5,10 @@ the flat gradient between backward and Adam.  One process per GPU; nothing here 
 
 The engine re-points the model's parameters at slices of the flat buffer, so ``model.state_dict()`` (reference
 key names, complex64 spectral weights) always reflects the trained weights and checkpoints stay interchangeable.
+
+Fine-tuning: parameters with ``requires_grad = False`` (or outside ``trainable=``) stay out of the flat buffers and keep their own storage;
+the backward pass stops behind the phase of the shallowest trainable tensor (``last_backward_phase``).  ``optimizer="adamw"`` runs
+decoupled weight decay inside the same optimiser launch (CFD_STEP_DECOUPLED_WD).
 """
 from __future__ import annotations
 
@@ -17,36 +21,99 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
-from ._capi import CFD_CLIP_FLOATS
+from ._capi import CFD_CLIP_FLOATS, CFD_STEP_DECOUPLED_WD
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
 _ACT_DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 
 
-def flatten_layout(params: Sequence[Tensor], align: int = 4) -> Tuple[List[int], int]:
-    """Offsets (in floats) of each tensor inside one flat fp32 buffer; complex tensors take 2 floats per element."""
+def flatten_layout(params: Sequence[Tensor], align: int = 4, trainable: Optional[Sequence[bool]] = None) -> Tuple[List[int], int]:
+    """Offsets (in floats) of each tensor inside one flat fp32 buffer; complex tensors take 2 floats per element.  ``trainable`` (one flag
+    per tensor; None = all): the COMPACT layout of a trainable subset -- same order, same alignment rule, a frozen tensor takes no room:
+    its offset is that of the next trainable tensor (or the total), so ``backward_phase_slices`` holds on the compact buffer as it is."""
     offs, off = [], 0
-    for p in params:
-        n = p.numel() * (2 if p.is_complex() else 1)
+    for i, p in enumerate(params):
+        n = p.numel() * (2 if p.is_complex() else 1) if trainable is None or trainable[i] else 0
         offs.append(off)
         off += (n + align - 1) // align * align
     return offs, off
 
 
-class FlatParams:
-    """One contiguous fp32 buffer holding every parameter; the module's Parameters become views of it."""
+def param_phase(i: int, num_layers: int) -> int:
+    """The backward phase that writes tensor i of ``abi_parameters`` (fc0 x2, four per FnoBlock, fc1 x2, fc2 x2): the head's four are
+    phase 0, FnoBlock l's are phase L - l, fc0's are phase L + 1."""
+    if not 0 <= i < 6 + 4 * num_layers:
+        raise IndexError(f"tensor {i} of a model with {num_layers} FnoBlocks")
+    if i < 2:
+        return num_layers + 1
+    if i >= 2 + 4 * num_layers:
+        return 0
+    return num_layers - (i - 2) // 4
 
-    def __init__(self, params: Sequence[torch.nn.Parameter]):
+
+def last_backward_phase(trainable: Sequence[bool], num_layers: int) -> int:
+    """The last backward phase a pass must run for its trainable tensors (one flag per tensor, ``abi_parameters`` order): the phase of the
+    SHALLOWEST trainable tensor -- head only: 0 (with the one-pass head no backward-phase call is made at all), FnoBlock l: L - l, fc0:
+    L + 1.  A pass that must hand back the gradient of its inputs (``grads->d_inputs``) runs all L + 2 phases whatever this says."""
+    if len(trainable) != 6 + 4 * num_layers:
+        raise ValueError(f"{len(trainable)} flags for a model of {6 + 4 * num_layers} tensors")
+    phases = [param_phase(i, num_layers) for i, t in enumerate(trainable) if t]
+    if not phases:
+        raise ValueError("nothing is trainable")
+    return max(phases)
+
+
+def mask_defer_flags(flags: int, fc0_trainable: bool, last_phase: int) -> int:
+    """The CFD_TRAIN_DEFER_* bits a pass over a trainable subset may keep.  CFD_TRAIN_DEFER_STEM (4) goes when fc0 is frozen: the optimiser
+    call would finish fc0's rows into the flat buffer, which holds no fc0.  CFD_TRAIN_DEFER_HEAD (2) goes when backward phase 1 does not
+    run: that phase carries the head's reduction.  CFD_TRAIN_DEFER_SCALE (1) stays: the optimiser call applies the factor to whatever the
+    flat gradient holds.  All trainable: the flags as they are."""
+    if not fc0_trainable:
+        flags &= ~4
+    if last_phase < 1:
+        flags &= ~2
+    return flags
+
+
+def match_prefixes(names: Sequence[str], prefixes: Sequence[str]) -> List[bool]:
+    """One flag per name: whether a state_dict key prefix covers it (``blocks.1`` covers ``blocks.1.w0.weight``, not ``blocks.10...``; a
+    full key covers itself).  A prefix that covers nothing is an error."""
+    prefixes = [q.rstrip(".") for q in prefixes]
+    covers = lambda q, k: k == q or k.startswith(q + ".")  # noqa: E731
+    for q in prefixes:
+        if not q or not any(covers(q, k) for k in names):
+            raise ValueError(f"prefix {q!r} matches no parameter (keys: {', '.join(names)})")
+    return [any(covers(q, k) for q in prefixes) for k in names]
+
+
+class FlatParams:
+    """One contiguous fp32 buffer holding every TRAINABLE parameter (``trainable``: one flag per tensor, None = all); the module's
+    trainable Parameters become views of it.  A frozen parameter keeps its own (contiguous) storage -- ``views`` holds a float view of
+    it, so ``ptrs()`` serves the ``params`` struct alike -- and its entry of ``grad_views`` lies in ``sink``, a scratch buffer the
+    backward phases may write (they write every gradient tensor of their layer) and nothing reads."""
+
+    def __init__(self, params: Sequence[torch.nn.Parameter], trainable: Optional[Sequence[bool]] = None):
         self.params = list(params)
+        self.trainable = [True] * len(self.params) if trainable is None else [bool(t) for t in trainable]
         dev = self.params[0].device
-        self.offsets, self.numel = flatten_layout(self.params)
+        self.offsets, self.numel = flatten_layout(self.params, trainable=self.trainable)
         self.data = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        frozen = [not t for t in self.trainable]
+        sink_offs, sink_numel = flatten_layout(self.params, trainable=frozen)
+        self.sink = torch.empty(sink_numel, dtype=torch.float32, device=dev) if sink_numel else None
         self.views: List[Tensor] = []
         self.grad_views: List[Tensor] = []
-        for p, off in zip(self.params, self.offsets):
+        for p, off, soff, t in zip(self.params, self.offsets, sink_offs, self.trainable):
             n = p.numel() * (2 if p.is_complex() else 1)
+            if not t:
+                if p.dtype not in (torch.float32, torch.complex64):
+                    raise TypeError("FlatParams: a frozen parameter must be float32 or complex64")
+                p.data = p.detach().contiguous()
+                self.views.append((torch.view_as_real(p.data) if p.is_complex() else p.data).reshape(-1))
+                self.grad_views.append(self.sink[soff:soff + n])
+                continue
             sl = self.data[off:off + n]
             gsl = self.grad[off:off + n]
             if p.is_complex():
@@ -269,8 +336,18 @@ class FnoTrainEngine:
 
     def __init__(self, model, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
-                 overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None):
-        """``max_grad_norm``: global gradient-norm clipping inside the optimiser call (cfd_fno_params.clip; the semantics of
+                 overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None,
+                 trainable: Optional[Sequence[str]] = None, optimizer: str = "adam"):
+        """``trainable``: state_dict key prefixes (``{"fc1", "fc2"}``, ``{"blocks.3", "fc1", "fc2"}``) of the parameters to train; the
+        others are frozen (their ``requires_grad`` is set to match).  None: the engine honours ``requires_grad`` as it finds it.  The
+        flat buffers (parameters, gradient, moments, accumulator, what a data-parallel run exchanges) hold the trainable tensors only, and
+        the backward pass stops behind the phase of the shallowest one (``last_backward_phase``); ``gradients()`` and ``grad_norm()`` are
+        those of the trainable subset -- what ``clip_grad_norm_`` over the trainable parameters sees.  Nothing trainable: ValueError.
+
+        ``optimizer``: "adam" (``weight_decay`` is L2, coupled: added to the gradient) or "adamw" (decoupled, torch.optim.AdamW's rule:
+        CFD_STEP_DECOUPLED_WD of cfd_fno_adam_step, which is then the optimiser call on every route).
+
+        ``max_grad_norm``: global gradient-norm clipping inside the optimiser call (cfd_fno_params.clip; the semantics of
         ``torch.nn.utils.clip_grad_norm_`` with norm_type 2, taken of the gradient Adam applies -- after the deferred normaliser, the
         lifting layer's rows and, data-parallel, the all-reduce and its 1 / world).  None: no clipping, the calls of an engine without
         the argument; ``float("inf")``: the norm is measured (``grad_norm()``) and nothing is clipped.  One launch more per step.
@@ -286,15 +363,31 @@ class FnoTrainEngine:
         self.act_dtype = _ACT_DTYPES[act_dtype]
         if self.act_dtype and not fused_head:
             raise ValueError("bf16 activation storage runs the one-pass training head: fused_head must be True")
+        if optimizer not in ("adam", "adamw"):
+            raise ValueError("optimizer must be 'adam' or 'adamw'")
+        self.optimizer = optimizer
+        self._dw_flag = CFD_STEP_DECOUPLED_WD if optimizer == "adamw" else 0  # (beside the pass's flags in every optimiser call)
         self.api = _lib.api()
         self.model = model
         params = model.abi_parameters()
         if not params[0].is_cuda:
             raise RuntimeError("FnoTrainEngine: move the model to the GPU first (no CPU fallback)")
         self.device = params[0].device
-        self.flat = FlatParams(params)
         self.cfg = model.abi_config()
         self.L = self.cfg["num_layers"]
+        key_of = {id(p_): k for k, p_ in model.named_parameters()}
+        self.param_names = [key_of[id(p_)] for p_ in params]
+        if trainable is not None:
+            for p_, t in zip(params, match_prefixes(self.param_names, sorted(trainable))):
+                p_.requires_grad_(t)
+        mask = [bool(p_.requires_grad) for p_ in params]
+        if not any(mask):
+            raise ValueError("FnoTrainEngine: nothing is trainable (every parameter of the model is frozen)")
+        self.all_trainable = all(mask)
+        self.trainable_names = [k for k, t in zip(self.param_names, mask) if t]
+        # the last backward phase of a pass (all trainable: L + 1, every phase)
+        self.last_phase = last_backward_phase(mask, self.L)
+        self.flat = FlatParams(params, None if self.all_trainable else mask)
         self.exp_avg = torch.zeros_like(self.flat.data)
         self.exp_avg_sq = torch.zeros_like(self.flat.data)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
@@ -311,7 +404,9 @@ class FnoTrainEngine:
         # CFD_TRAIN_DEFER_*: the nMSE normaliser into Adam, the head's reduction into backward phase 1, the fc0 combine into Adam's
         # launch).  Data-parallel steps keep them: a rank's gradients must be final and normalised by ITS labels before the all-reduce.
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
-        self.defer_flags = 0 if (self.sync.exchange or not fused_head) else 7
+        # A trainable subset keeps the flags whose carrier still runs and whose result has a place (mask_defer_flags).  The normaliser's
+        # flag is never dropped, so what reads `_route_defers` (optimizer_step, for gradients()) holds for a subset as it is.
+        self.defer_flags = mask_defer_flags(0 if (self.sync.exchange or not fused_head) else 7, mask[0], self.last_phase)
         self._route_defers = False  # whether the batch's route honours the flags: known per batch (_prepare, _lib.fno_call)
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
@@ -355,13 +450,18 @@ class FnoTrainEngine:
         model, data, sums, coef, ws, st = self._begin(inputs, label, case_params, mask, flags)
         if self.fused_head:
             a.call("cfd_fno_forward_train_f", *model, *data, sums, coef, ws, self.loss_id, 1.0, self.act_dtype, flags, st)
-            for phase in range(1, self.L + 2):  # phase 0 (the head) left the fused kernel already
+            # phase 0 (the head) left the fused kernel already; a trainable subset stops behind its shallowest tensor's phase
+            for phase in range(1, self.last_phase + 1):
                 a.call("cfd_fno_backward_phase_f", *model, *data, None, coef, sums, ws, phase, self.loss_id, self.act_dtype, flags, st)
             return
         if flags:
             raise RuntimeError("FnoTrainEngine: the deferred training step needs the one-pass head (fused_head)")
         self._forward_two_pass_head(model, data, sums, coef, ws, st)
-        a.call("cfd_fno_backward", *model, *data, None, coef, ws, st)
+        if self.all_trainable:
+            a.call("cfd_fno_backward", *model, *data, None, coef, ws, st)
+            return
+        for phase in range(self.last_phase + 1):  # (cfd_fno_backward is every phase: a subset walks the phase entry itself)
+            a.call("cfd_fno_backward_phase_ex", *model, *data, None, coef, ws, phase, self.act_dtype, st)
 
     def _begin(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor], flags: int):
         """What every pass starts with: the tensor check, the per-shape state, and the arguments its C calls share --
@@ -384,7 +484,8 @@ class FnoTrainEngine:
     def phase_slices(self) -> List[Tuple[int, int]]:
         """[start, stop) of the flat gradient buffer written by backward phase k (cfd_fno_backward_phase): phase 0 = head
         (fc1, fc2: the last four tensors), phase 1 .. L = FnoBlock L-k (four tensors each), phase L+1 = fc0 (the first
-        two).  ``abi_parameters`` order is fc0, blocks 0 .. L-1, fc1, fc2, so every phase owns one contiguous slice."""
+        two).  ``abi_parameters`` order is fc0, blocks 0 .. L-1, fc1, fc2, so every phase owns one contiguous slice.  With a
+        trainable subset the buffer is compact: a phase's slice covers its trainable tensors and is empty where it has none."""
         return backward_phase_slices(self.flat.offsets, self.flat.numel, self.L)
 
     def forward_backward_overlapped(self, inputs: Tensor, label: Tensor, case_params: Tensor,
@@ -439,7 +540,9 @@ class FnoTrainEngine:
         if self.accum is None:
             self.accum = torch.zeros_like(self.flat.grad)
             base, g0 = self.accum.data_ptr(), self.flat.grad.data_ptr()
-            self.astruct = _param_struct([base + (p_ - g0) for p_ in self.flat.ptrs(True)], self.L)
+            # (a frozen tensor's entry stays in the sink: the accumulate call touches the flat buffers and, under CFD_TRAIN_DEFER_STEM --
+            # kept only with fc0 trainable -- fc0's rows)
+            self.astruct = _param_struct([base + (p_ - g0) if t else p_ for p_, t in zip(self.flat.ptrs(True), self.flat.trainable)], self.L)
             if self.clip is not None:  # (read where the struct is the `grads` of the optimiser call on the accumulator)
                 self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
 
@@ -538,7 +641,8 @@ class FnoTrainEngine:
         for k in range(K - 1, -1, -1):
             gr, data, sums, coef, ws = args(k)
             gext = w["dx"][k % 2].data_ptr() if k < K - 1 else None  # = d_inputs of step k + 1 (1-based k + 2: dx[(k + 2) % 2])
-            for phase in range(1 if one_pass[k] else 0, self.L + 2):
+            # step k + 1 >= 2 hands d loss / d x back to the step before it: every phase; the window's first step stops where a plain pass does
+            for phase in range(1 if one_pass[k] else 0, (self.L + 1 if k >= 1 else self.last_phase) + 1):
                 a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *data, gext, coef, sums, ws, phase, self.loss_id, 0, 0, st)
             flags = CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if (first and k == K - 1) else 0)
             a.call("cfd_fno_adam_step", plan, sh, ctypes.byref(self.astruct), gr, data[0], cp, mk, sums, ws, self.accum.data_ptr(),
@@ -569,10 +673,13 @@ class FnoTrainEngine:
                       inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
                       self.ws.data_ptr(), self.flat.data.data_ptr(), self.accum.data_ptr(), self.exp_avg.data_ptr(),
                       self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                      self.step_count, scale, self.loss_id, self.act_dtype, 0, torch.cuda.current_stream().cuda_stream)
+                      self.step_count, scale, self.loss_id, self.act_dtype, self._step_flags(0), torch.cuda.current_stream().cuda_stream)
         self._accum_open = False
         self._grad_pending_scale = False
         self._grad_in_accum = True
+
+    def _step_flags(self, flags: int) -> int:
+        return flags | self._dw_flag
 
     def optimizer_step(self, grad_scale: float = 1.0):
         self._no_open_group("optimizer_step")
@@ -581,15 +688,17 @@ class FnoTrainEngine:
         inputs, case_params, mask, flags = getattr(self, "_last", (None, None, None, 0))
         # the pass left work to this launch (nMSE normaliser from sums[2:4], the lifting layer's gradient rows), or the step clips: the
         # norm is taken inside cfd_fno_adam_step, which with flags = 0 is cfd_adam_flat otherwise
-        if self.clip is not None and inputs is None:
-            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping needs the pass that produced the gradients "
+        adamw = self._dw_flag != 0  # (decoupled decay exists in cfd_fno_adam_step alone: the optimiser call on every route)
+        if (self.clip is not None or adamw) and inputs is None:
+            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping and AdamW need the pass that produced the gradients "
                                "(forward_backward / train_step) first")
-        if flags or self.clip is not None:
+        if flags or self.clip is not None or adamw:
             self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
                           inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
                           self.ws.data_ptr(), self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                           self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                          self.step_count, grad_scale, self.loss_id, self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
+                          self.step_count, grad_scale, self.loss_id, self.act_dtype, self._step_flags(flags),
+                          torch.cuda.current_stream().cuda_stream)
             self._last = (inputs, case_params, mask, 0)  # (a second optimizer_step on the same gradients must not redo the deferred work)
             self._grad_pending_scale = bool(flags & 1) and self.loss_id == _LOSS_IDS["nmse"] and self._route_defers
             return
@@ -602,7 +711,8 @@ class FnoTrainEngine:
         """The flat gradient of the last step in the loss's own units, UNCLIPPED (with ``max_grad_norm`` Adam applied it times
         ``clip_coef()``; the buffer is never clipped).  After a deferred train_step (``defer_flags``) the buffer holds the gradients of
         sum d^2 / n -- this returns them times n / sum (label*mask)^2; otherwise the buffer itself (data-parallel: the sum over ranks).
-        After ``apply_accumulated`` it is the accumulator: the weighted sum over the group's micro-batches, final."""
+        After ``apply_accumulated`` it is the accumulator: the weighted sum over the group's micro-batches, final.  With a trainable
+        subset the buffer is compact: the trainable tensors in ``abi_parameters`` order (``flat.offsets``)."""
         if self._grad_in_accum:
             return self.accum
         if getattr(self, "_grad_pending_scale", False):
@@ -625,7 +735,8 @@ class FnoTrainEngine:
         """One optimisation step; returns the device tensor [sum sq err, sum abs err, sum sq label, n] of THIS rank's
         batch (no host sync -- read it with .tolist() only when logging)."""
         self._no_open_group("train_step")
-        if self.sync.exchange and self.overlap:
+        # (a frozen subset exchanges its compact gradient once, behind the pass: the per-phase exchange is the all-trainable engine's)
+        if self.sync.exchange and self.overlap and self.all_trainable:
             scale = self.forward_backward_overlapped(inputs, label, case_params, mask)
         else:
             self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
@@ -638,9 +749,13 @@ class FnoTrainEngine:
         """Adam moments (flat, in ``abi_parameters`` order), step count and learning rate.  The weights themselves live in
         the model's ``state_dict`` (the flat buffer is what the model's parameters view)."""
         return dict(exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
-                    step_count=int(self.step_count), lr=float(self.lr), numel=int(self.flat.numel))
+                    step_count=int(self.step_count), lr=float(self.lr), numel=int(self.flat.numel), trainable=list(self.trainable_names))
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
+        # (a state from before the key existed is an all-trainable engine's)
+        theirs = list(state.get("trainable", self.param_names))
+        if theirs != self.trainable_names:
+            raise ValueError(f"optimiser state is for the trainable tensors {theirs}, the engine trains {self.trainable_names}")
         if int(state["numel"]) != int(self.flat.numel):
             raise ValueError(f"optimiser state is for {state['numel']} parameters, the model has {self.flat.numel}")
         self.exp_avg.copy_(state["exp_avg"].to(self.device))
@@ -671,7 +786,7 @@ class FnoTrainEngine:
         torch.cuda.synchronize()  # (no collective of an earlier step in flight: see graph.CAPTURE_MODE)
         # Round 6: over RCCL the per-phase all-reduces are captured with the pass (forked onto the communicator's stream and joined back
         # by events), so a replayed data-parallel step makes no host call into the process group; host-staged backends reduce after it.
-        self._graph_exchanges = bool(self.sync.exchange and self.sync.device_native and self.overlap
+        self._graph_exchanges = bool(self.sync.exchange and self.sync.device_native and self.overlap and self.all_trainable
                                      and os.environ.get("CFDBENCH_DP_ONE_GRAPH", "1") != "0")
         with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
             if self._graph_exchanges:

@@ -24,7 +24,14 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``max_grad_norm`` (> 0: global gradient-norm clipping at that threshold before every optimiser step -- --fused 1: inside the engine's
     optimiser call, eager paths: torch.nn.utils.clip_grad_norm_; 0.0 = off; not with --graph 1),
     ``fused_accumulation_steps`` (train_auto --fused 1, N > 1: N micro-batches per fused optimiser step -- FnoTrainEngine.accumulate /
-    apply_accumulated; what --gradient_accumulation_steps is to the autograd path; not with --graph 1).
+    apply_accumulated; what --gradient_accumulation_steps is to the autograd path; not with --graph 1),
+    ``freeze`` / ``train_only`` (comma-separated state_dict key prefixes, mutually exclusive: the parameters they cover are frozen /
+    are the only ones trained -- ``requires_grad_`` on any model, before the optimiser or engine is built; a prefix that matches nothing
+    is an error; --fused 1: FnoTrainEngine trains the subset on compact buffers and stops the backward pass behind its shallowest tensor),
+    ``optimizer`` (adam = the reference's loop, ``weight_decay`` still unused as there | adamw = decoupled decay by ``weight_decay``:
+    torch.optim.AdamW on the eager paths, FnoTrainEngine(optimizer="adamw") with --fused 1; not with --graph 1),
+    ``init_from`` (a model.pt to load through ``load_ckpt`` before training: fine-tuning from another run's weights; ignored, with a log
+    line, when --resume 1 finds a train_state.pt).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -55,7 +62,7 @@ _FLAGS: Dict[str, Any] = dict(
     # additions of this harness
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
-    fused_accumulation_steps=1, unroll_detach=0,
+    fused_accumulation_steps=1, unroll_detach=0, freeze="", train_only="", optimizer="adam", init_from="",
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -131,6 +138,10 @@ def is_args_valid(args: Args) -> None:
             assert args.gradient_accumulation_steps == 1, "--unroll_steps > 1 on the autograd path needs gradient_accumulation_steps == 1"
     else:
         assert not args.unroll_detach, "--unroll_detach 1 is an option of --unroll_steps > 1"
+    assert not (args.freeze and args.train_only), "--freeze and --train_only are mutually exclusive: give one of them"
+    assert args.optimizer in ("adam", "adamw"), "--optimizer is adam (weight_decay unused, as in the reference) or adamw (decoupled decay)"
+    if args.graph:
+        assert args.optimizer == "adam", "--graph 1 with --optimizer adamw is not built: cfd_adam_multi has no decoupled form"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import json
 from pathlib import Path
-from typing import Optional, Union
+from typing import List, Optional, Union
 
 import torch
 
@@ -64,6 +64,40 @@ def get_best_ckpt(output_dir: Path) -> Union[Path, None]:
 def load_ckpt(model, ckpt_path: Path) -> None:  # common.py:177-179
     print(f"Loading checkpoint from {ckpt_path}")
     model.load_state_dict(torch.load(ckpt_path, map_location="cpu"))
+
+
+def split_prefixes(text: str) -> List[str]:
+    """``--freeze a,b`` / ``--train_only a,b`` -> ["a", "b"]."""
+    return [q.strip() for q in (text or "").split(",") if q.strip()]
+
+
+def apply_trainable(model, freeze: str = "", train_only: str = "") -> List[str]:
+    """--freeze / --train_only on any model: ``requires_grad_`` by state_dict key prefix (engine.match_prefixes: a prefix that matches
+    nothing is an error), before the optimiser or engine is built.  Returns the names left trainable."""
+    from ..engine import match_prefixes
+    fr, only = split_prefixes(freeze), split_prefixes(train_only)
+    if fr and only:
+        raise ValueError("--freeze and --train_only are mutually exclusive")
+    named = list(model.named_parameters())
+    names = [k for k, _ in named]
+    if fr or only:
+        hit = match_prefixes(names, fr or only)
+        for (_, p_), h in zip(named, hit):
+            p_.requires_grad_(h != bool(fr))
+    left = [k for k, p_ in named if p_.requires_grad]
+    if not left:
+        raise ValueError("--freeze / --train_only leave nothing trainable")
+    return left
+
+
+def make_optimizer(params, kind: str, lr, weight_decay: float = 0.0, **kw):
+    """The eager paths' optimiser: adam = torch.optim.Adam as in the reference (``weight_decay`` is not passed, as there); adamw =
+    torch.optim.AdamW with ``weight_decay``, decoupled."""
+    if kind == "adam":
+        return torch.optim.Adam(params, lr=lr, **kw)
+    if kind == "adamw":
+        return torch.optim.AdamW(params, lr=lr, weight_decay=float(weight_decay), **kw)
+    raise ValueError("optimizer must be 'adam' or 'adamw'")
 
 
 def load_best_ckpt(model, output_dir: Path) -> Path:  # common.py:278-284

@@ -28,7 +28,8 @@ from ..models.deeponet import DeepONet
 from ..models.ffn import FfnModel
 from ..models.loss import loss_name_to_fn
 from .args import Args, is_args_valid
-from .common import dump_json, get_output_dir, load_best_ckpt, plot_loss, plot_predictions
+from .common import (apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot_loss,
+                     plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
                         shard_indices)
@@ -100,8 +101,11 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
           eval_interval: int = 2, measure_time: bool = False, plot_interval: int = 1, resume: bool = False,
           lr_scheduler_kind: str = "step", lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5,
           early_stopping_patience: int = 0, early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1,
-          graph: bool = False, max_grad_norm: float = 0.0):
+          graph: bool = False, max_grad_norm: float = 0.0, optimizer_kind: str = "adam", weight_decay: float = 0.0,
+          init_from: str = ""):
     """src/train.py:148-253: fwd -> ``loss["nmse"].backward()`` -> Adam -> zero_grad; StepLR per epoch.
+    ``optimizer_kind`` / ``weight_decay`` / ``init_from`` and the model's ``requires_grad`` flags (--freeze / --train_only): as
+    harness/train_auto.py:train.
     ``graph``: the step replayed from HIP graphs (harness/train_auto.py:train has the semantics; no accumulation; several ranks: graph.py).
     ``resume``: continue from ``train_state.pt`` (see harness/train_auto.py:train).  ``lr_scheduler_kind`` /
     ``early_stopping_patience`` / ``gradient_accumulation_steps``: the same options, with the same semantics, as
@@ -126,6 +130,14 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
     if rank == 0:
         output_dir.mkdir(exist_ok=True, parents=True)
     accum = max(1, int(gradient_accumulation_steps))
+    if optimizer_kind == "adamw" and graph:
+        raise NotImplementedError("--optimizer adamw needs --graph 0: cfd_adam_multi has no decoupled form")
+    if init_from:
+        if resume and (output_dir / "train_state.pt").exists():
+            if rank == 0:
+                print(f"--init_from {init_from} ignored: --resume 1 continues from {output_dir / 'train_state.pt'}")
+        else:
+            load_ckpt(model, Path(init_from))
     if graph:
         if accum > 1:
             raise NotImplementedError("--graph 1 needs gradient_accumulation_steps == 1")
@@ -138,7 +150,7 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
             optimizer = Adam(model.parameters(), lr=torch.tensor(float(lr), device="cuda"), capturable=True,
                              fused=not any(p_.is_complex() for p_ in model.parameters()))  # (torch's fused form takes real parameters only)
     else:
-        optimizer = Adam(model.parameters(), lr=lr)
+        optimizer = make_optimizer(model.parameters(), optimizer_kind, lr, weight_decay)
     graphed = None
     schedule = LrSchedule(lr_scheduler_kind, lr, num_epochs, optimizer, lr_step_size=lr_step_size, lr_gamma=lr_gamma,
                           factor=lr_scheduler_factor, patience=lr_scheduler_patience)
@@ -320,8 +332,11 @@ def main(argv=None):
     train_data, dev_data, test_data = get_dataset(Path(args.data_dir), args.data_name, bool(args.norm_props),
                                                   bool(args.norm_bc))
     model = init_model(args).cuda()
+    left = apply_trainable(model, args.freeze, args.train_only)
     if rank == 0:
         print(f"Model has {sum(p.numel() for p in model.parameters())} parameters")
+        if args.freeze or args.train_only:
+            print(f"Training {len(left)} of {len(list(model.parameters()))} tensors: {', '.join(left)}")
     if "train" in args.mode:
         if rank == 0:
             args.save(str(output_dir / "train_args.json"))
@@ -332,7 +347,8 @@ def main(argv=None):
               lr_scheduler_patience=args.lr_scheduler_patience,
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
-              graph=bool(args.graph), max_grad_norm=args.max_grad_norm)
+              graph=bool(args.graph), max_grad_norm=args.max_grad_norm, optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
+              init_from=args.init_from)
     if "test" in args.mode and rank == 0:
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

@@ -34,7 +34,8 @@ from ..models.fno.fno2d import Fno2d
 from ..unroll import collate_windows, unroll_windows, unrolled_loss
 from .args import Args, is_args_valid
 from .autoregressive import init_model
-from .common import dump_json, get_output_dir, load_best_ckpt, plot, plot_loss, plot_predictions
+from .common import (apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
+                     plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
                         shard_indices)
@@ -179,8 +180,15 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           plot_interval: int = 1, resume: bool = False, device_loader: bool = False, lr_scheduler_kind: str = "step",
           lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5, early_stopping_patience: int = 0,
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
-          unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False):
+          unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False, optimizer_kind: str = "adam",
+          weight_decay: float = 0.0, init_from: str = ""):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
+
+    Fine-tuning: the model's ``requires_grad`` flags are honoured on every path (``common.apply_trainable``: --freeze / --train_only set
+    them before this is called) -- the eager optimisers skip a parameter without gradient, the fused engine trains the subset on compact
+    buffers.  ``optimizer_kind`` = "adamw": decoupled decay by ``weight_decay`` (torch.optim.AdamW eagerly, FnoTrainEngine(optimizer=
+    "adamw") fused; not with ``graph``); "adam" is the reference's loop and never reads ``weight_decay``.  ``init_from``: a model.pt loaded
+    through ``load_ckpt`` before the engine or optimiser is built; a ``resume`` that finds its train_state.pt ignores it, with a log line.
 
     ``graph`` (autograd path; with several ranks the gradient exchange sits between two graphs, cfdbench_amd/graph.py): the step ``model(**batch) -> loss["nmse"].backward() -> Adam.step()`` is captured once
     as a HIP graph (cfdbench_amd/graph.py) at the first full batch and replayed for every batch of that shape; a short last batch
@@ -280,12 +288,24 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     train_loader = make_loader(0)
     if rank == 0:
         output_dir.mkdir(exist_ok=True, parents=True)
+    if optimizer_kind not in ("adam", "adamw"):
+        raise ValueError("optimizer_kind must be 'adam' or 'adamw'")
+    if optimizer_kind == "adamw" and graph:
+        raise NotImplementedError("--optimizer adamw needs --graph 0: cfd_adam_multi has no decoupled form")
+    if init_from:
+        if resume and (output_dir / "train_state.pt").exists():
+            if rank == 0:
+                print(f"--init_from {init_from} ignored: --resume 1 continues from {output_dir / 'train_state.pt'}")
+        else:
+            load_ckpt(model, Path(init_from))
     engine = None
     accum = max(1, int(gradient_accumulation_steps))
     if fused:
         if not isinstance(model, Fno2d):
             raise NotImplementedError("--fused 1 needs the fno model")
-        engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None)
+        # (adam: weight_decay stays unused, as in the reference)
+        engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None,
+                                optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0)
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -301,7 +321,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             optimizer = Adam(model.parameters(), lr=torch.tensor(float(lr), device="cuda"), capturable=True,
                              fused=not any(p_.is_complex() for p_ in model.parameters()))  # (torch's fused form takes real parameters only)
     else:
-        optimizer = Adam(model.parameters(), lr=lr)
+        optimizer = make_optimizer(model.parameters(), optimizer_kind, lr, weight_decay)
     graphed = None
     schedule = LrSchedule(lr_scheduler_kind, lr, num_epochs, optimizer, lr_step_size=lr_step_size, lr_gamma=lr_gamma,
                           factor=lr_scheduler_factor, patience=lr_scheduler_patience)
@@ -513,8 +533,11 @@ def main(argv=None):
         data_dir=Path(args.data_dir), data_name=args.data_name, delta_time=args.delta_time,
         norm_props=bool(args.norm_props), norm_bc=bool(args.norm_bc))
     model = init_model(args).cuda()  # the reference forgets .cuda() for FNO
+    left = apply_trainable(model, args.freeze, args.train_only)
     if rank == 0:
         print(f"Model has {sum(p.numel() for p in model.parameters())} parameters")
+        if args.freeze or args.train_only:
+            print(f"Training {len(left)} of {len(list(model.parameters()))} tensors: {', '.join(left)}")
     if "train" in args.mode:
         if rank == 0:
             args.save(str(output_dir / "train_args.json"))
@@ -528,7 +551,8 @@ def main(argv=None):
               early_stopping_delta=args.early_stopping_delta,
               gradient_accumulation_steps=args.fused_accumulation_steps if args.fused else args.gradient_accumulation_steps,
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
-              unroll_detach=bool(args.unroll_detach))
+              unroll_detach=bool(args.unroll_detach), optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
+              init_from=args.init_from)
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

@@ -611,12 +611,24 @@ int cfd_fno_backward_phase_ex(const cfd_plan* plan, const cfd_fno_shape* shape, 
  * One thread writes each element, no atomics: two calls give the same bits.  12 bytes per element, 8 with CFD_STEP_ACCUM_INIT.  param or
  * grad NULL: CFD_ERR_INVALID_ARG before any launch; n == 0: CFD_OK, nothing is launched.  The optimiser step on the accumulated gradient is
  * the call WITHOUT these bits: flags = 0, grad = the accumulator, `grads` pointing into it (with `clip` set when clipping).  Without
- * CFD_STEP_ACCUMULATE the call is what it was before the bits existed, bit for bit.                                                    */
+ * CFD_STEP_ACCUMULATE the call is what it was before the bits existed, bit for bit.
+ *
+ * Decoupled weight decay (AdamW; FnoTrainEngine(optimizer="adamw")) -- one more bit of cfd_fno_adam_step's `flags`, which the forward call
+ * and the backward phases never see either:
+ *   CFD_STEP_DECOUPLED_WD  `weight_decay` is decoupled from the gradient, in the operation order of torch.optim.AdamW's single-tensor path:
+ *                              param[i] *= f,  f = (float)(1.0 - (double)lr * (double)weight_decay)      (formed once, on the host)
+ *                              then the Adam update with the UNDECAYED gradient s * grad[i] (weight_decay is not added to it)
+ *                          grad_scale, the deferred normaliser, the fc0 rows under CFD_TRAIN_DEFER_STEM and the clip factor are what they
+ *                          are without the bit.  weight_decay == 0 with the bit: the bits of plain Adam.  Together with
+ *                          CFD_STEP_ACCUMULATE the bit is IGNORED: no hyper-parameter is read there; pass it with the optimiser call on
+ *                          the accumulator.  Without the bit the call is what it was before the bit existed, bit for bit (coupled L2
+ *                          decay: weight_decay * param is added to the gradient).  No launch more than Adam.                          */
 #define CFD_TRAIN_DEFER_SCALE 1
 #define CFD_TRAIN_DEFER_HEAD 2
 #define CFD_TRAIN_DEFER_STEM 4
 #define CFD_STEP_ACCUMULATE 8   /* cfd_fno_adam_step only */
 #define CFD_STEP_ACCUM_INIT 16  /* only together with CFD_STEP_ACCUMULATE */
+#define CFD_STEP_DECOUPLED_WD 32  /* cfd_fno_adam_step only; ignored with CFD_STEP_ACCUMULATE */
 int cfd_fno_forward_train_f(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params,
                             const cfd_fno_params* grads, const float* inputs, const float* case_params, const float* mask,
                             const float* label, float* preds, float* sums, float* coef, void* ws, int which, float upstream,
