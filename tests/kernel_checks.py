@@ -810,7 +810,10 @@ def check_deeponet_inner(be, B, P_, Kq, HW, with_q, seed=23):
 
 
 # ---- convolution stack of the U-Net / ResNet baselines (csrc/conv.hip) ------------------------------------------
-def check_conv2d(be, B, Ci, Co, H, W, ks, seed=31):
+def check_conv2d(be, B, Ci, Co, H, W, ks, seed=31, keep=None, want=("gin", "gw", "gb"), shift_in=0):
+    """`keep`: a dict that receives the inputs (x, w, b, g) and, under "got" / "ref", every output and its fp64 reference by name.
+    `want`: the outputs cfd_conv2d_bwd is asked for (the others are passed as NULL).  `shift_in`: bytes by which `in` is placed past
+    the 16-byte boundary (4 or 8)."""
     from oracle import conv_oracle as CO
     api, P = be.api, be.ptr
     rng = np.random.default_rng(seed)
@@ -818,23 +821,36 @@ def check_conv2d(be, B, Ci, Co, H, W, ks, seed=31):
     w = (rng.standard_normal((Co, Ci, ks, ks)) / np.sqrt(Ci * ks * ks)).astype(np.float32)
     b = rng.standard_normal((Co,)).astype(np.float32) * 0.2
     g = rng.standard_normal((B, Co, H, W)).astype(np.float32)
-    dx, dw, db, dg = be.dev(x), be.dev(w), be.dev(b), be.dev(g)
+    if shift_in:
+        with be.misaligned(shift_in):
+            dx = be.dev(x)
+    else:
+        dx = be.dev(x)
+    dw, db, dg = be.dev(w), be.dev(b), be.dev(g)
     out = be.out((B, Co, H, W))
     nws = api.size("cfd_conv2d_fwd_workspace_bytes", B, Ci, Co, H, W, ks)
     fws = be.scratch(nws) if nws else None
     api.call("cfd_conv2d_fwd", P(dx), P(dw), P(db), P(out), P(fws) if nws else None, B, Ci, Co, H, W, ks, be.stream)
     be.sync()
-    res = {"out": nm(be.host(out), CO.conv2d(x.astype(f64), w.astype(f64), b.astype(f64)))}
+    got = {"out": be.host(out)}
+    ref = {"out": CO.conv2d(x.astype(f64), w.astype(f64), b.astype(f64))}
     ws = be.scratch(api.size("cfd_conv2d_bwd_workspace_bytes", B, Ci, Co, H, W, ks))
-    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Co, Ci, ks, ks)), be.out((Co,))
-    api.call("cfd_conv2d_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, ks, be.stream)
+    outs = {"gin": be.out((B, Ci, H, W)), "gw": be.out((Co, Ci, ks, ks)), "gb": be.out((Co,))}
+    gin, gw, gb = (P(outs[k]) if k in want else None for k in ("gin", "gw", "gb"))
+    api.call("cfd_conv2d_bwd", P(dg), P(dx), P(dw), gin, gw, gb, P(ws), B, Ci, Co, H, W, ks, be.stream)
     be.sync()
-    rgx, rgw, rgb = CO.conv2d_bwd(g.astype(f64), x.astype(f64), w.astype(f64))
-    res["gin"], res["gw"], res["gb"] = nm(be.host(gin), rgx), nm(be.host(gw), rgw), nm(be.host(gb), rgb)
-    return res
+    ref["gin"], ref["gw"], ref["gb"] = CO.conv2d_bwd(g.astype(f64), x.astype(f64), w.astype(f64))
+    for k in ("gin", "gw", "gb"):
+        if k in want:
+            got[k] = be.host(outs[k])
+        elif keep is not None:  # (an output that was not asked for is not written: still poison from end to end)
+            keep.setdefault("untouched", {})[k] = be.host(outs[k])
+    if keep is not None:
+        keep.update(x=x, w=w, b=b, g=g, got=got, ref=ref)
+    return {k: nm(v, ref[k]) for k, v in got.items()}
 
 
-def check_conv2d_zeropad(be, B, Ci, Co, H, W, ks, seed=41):
+def check_conv2d_zeropad(be, B, Ci, Co, H, W, ks, seed=41, keep=None):
     """cfd_conv2d_zeropad_fwd / _bwd (nn.Conv2d's default zero padding on the conv6 kernels) against the fp64 oracle: the oracle's
     replicate-padded convolution of the input zero-padded by k / 2, cropped -- the construction the model used before -- and its
     reverse pass (gradient of the crop = zero-padding the upstream gradient; gradient of the pad = cropping)."""
@@ -860,7 +876,11 @@ def check_conv2d_zeropad(be, B, Ci, Co, H, W, ks, seed=41):
     xp, gp = np.pad(x.astype(f64), pad4), np.pad(g.astype(f64), pad4)
     ref = CO.conv2d(xp, w.astype(f64), b.astype(f64))[:, :, p:-p, p:-p]
     rgx, rgw, rgb = CO.conv2d_bwd(gp, xp, w.astype(f64))
-    return {"out": nm(be.host(out), ref), "gin": nm(be.host(gin), rgx[:, :, p:-p, p:-p]), "gw": nm(be.host(gw), rgw), "gb": nm(be.host(gb), rgb)}
+    got = {"out": be.host(out), "gin": be.host(gin), "gw": be.host(gw), "gb": be.host(gb)}
+    refs = {"out": ref, "gin": rgx[:, :, p:-p, p:-p], "gw": rgw, "gb": rgb}
+    if keep is not None:  # (as in check_conv2d)
+        keep.update(x=x, w=w, b=b, g=g, got=got, ref=refs)
+    return {k: nm(v, refs[k]) for k, v in got.items()}
 
 
 def check_conv_prepared(be, layers, seed=37):
@@ -912,7 +932,7 @@ def check_conv_prepared(be, layers, seed=37):
     return bad
 
 
-def check_conv_bn_stats(be, B, Ci, Co, H, W, ks, relu=True, seed=36, offset=0.0, spread=1.0):
+def check_conv_bn_stats(be, B, Ci, Co, H, W, ks, relu=True, seed=36, offset=0.0, spread=1.0, keep=None):
     """cfd_conv2d_fwd_stats + cfd_batchnorm_fwd_stats (the conv emits the BatchNorm's batch statistics) against the oracle's
     conv -> training-mode BatchNorm; returns None when the layer cannot emit statistics.  `offset` / `spread`: input = offset +
     spread * noise under all-positive weights -- output channels whose mean is far from the bias and |mean| >> std."""
@@ -941,6 +961,8 @@ def check_conv_bn_stats(be, B, Ci, Co, H, W, ks, relu=True, seed=36, offset=0.0,
     be.sync()
     r0 = CO.conv2d(x.astype(f64), w.astype(f64), b.astype(f64))
     ry, cache, nrm, nrv = CO.batchnorm(r0, gamma.astype(f64), beta.astype(f64), rm.astype(f64), rv.astype(f64), True, relu=relu)
+    if keep is not None:  # (as in check_conv2d; the convolution's own output only)
+        keep.update(x=x, w=w, b=b, got={"out": be.host(out)}, ref={"out": r0})
     return {"out": nm(be.host(out), r0), "y": nm(be.host(y), ry), "run_mean": nm(be.host(drm), nrm), "run_var": nm(be.host(drv), nrv)}
 
 
@@ -972,14 +994,20 @@ def check_batchnorm(be, B, C, H, W, training, relu, seed=32):
     return res
 
 
-def check_convt(be, B, Ci, Co, H, W, seed=34, x=None, rng=None):
-    """cfd_convt2_fwd / cfd_convt2_bwd (ConvTranspose2d(2, stride 2), unet.py:80) against the oracle"""
+def check_convt(be, B, Ci, Co, H, W, seed=34, x=None, rng=None, keep=None, want=("gin", "gw", "gb"), shift_in=0):
+    """cfd_convt2_fwd / cfd_convt2_bwd (ConvTranspose2d(2, stride 2), unet.py:80) against the oracle.  `keep`, `want`: as in
+    check_conv2d (names convt, convt_gin, convt_gw, convt_gb).  `shift_in`: bytes by which `in` is placed past the 16-byte boundary (4 or 8:
+    the matrix-pipe weight gradient then leaves the call to the fp32 kernel)."""
     from oracle import conv_oracle as CO
     api, P = be.api, be.ptr
     rng = rng if rng is not None else np.random.default_rng(seed)
     if x is None:
         x = np.maximum(rng.standard_normal((B, Ci, H, W)), 0).astype(np.float32)
-    dx = be.dev(x)
+    if shift_in:
+        with be.misaligned(shift_in):
+            dx = be.dev(x)
+    else:
+        dx = be.dev(x)
     w = (rng.standard_normal((Ci, Co, 2, 2)) / np.sqrt(Ci)).astype(np.float32)
     b = rng.standard_normal((Co,)).astype(np.float32) * 0.1
     g = rng.standard_normal((B, Co, 2 * H, 2 * W)).astype(np.float32)
@@ -987,13 +1015,18 @@ def check_convt(be, B, Ci, Co, H, W, seed=34, x=None, rng=None):
     out = be.out((B, Co, 2 * H, 2 * W))
     api.call("cfd_convt2_fwd", P(dx), P(dw), P(db), P(out), B, Ci, Co, H, W, be.stream)
     ws = be.scratch(api.size("cfd_convt2_bwd_workspace_bytes", B, Ci, Co, H, W))
-    gin, gw, gb = be.out((B, Ci, H, W)), be.out((Ci, Co, 2, 2)), be.out((Co,))
-    api.call("cfd_convt2_bwd", P(dg), P(dx), P(dw), P(gin), P(gw), P(gb), P(ws), B, Ci, Co, H, W, be.stream)
+    outs = {"gin": be.out((B, Ci, H, W)), "gw": be.out((Ci, Co, 2, 2)), "gb": be.out((Co,))}
+    gin, gw, gb = (P(outs[k]) if k in want else None for k in ("gin", "gw", "gb"))
+    api.call("cfd_convt2_bwd", P(dg), P(dx), P(dw), gin, gw, gb, P(ws), B, Ci, Co, H, W, be.stream)
     be.sync()
-    res = {"convt": nm(be.host(out), CO.convt2(x.astype(f64), w.astype(f64), b.astype(f64)))}
-    rgx, rgw, rgb = CO.convt2_bwd(g.astype(f64), x.astype(f64), w.astype(f64))
-    res["convt_gin"], res["convt_gw"], res["convt_gb"] = nm(be.host(gin), rgx), nm(be.host(gw), rgw), nm(be.host(gb), rgb)
-    return res
+    got = {"convt": be.host(out)}
+    ref = {"convt": CO.convt2(x.astype(f64), w.astype(f64), b.astype(f64))}
+    ref["convt_gin"], ref["convt_gw"], ref["convt_gb"] = CO.convt2_bwd(g.astype(f64), x.astype(f64), w.astype(f64))
+    for k in want:
+        got["convt_" + k] = be.host(outs[k])
+    if keep is not None:
+        keep.update(x=x, w=w, b=b, g=g, got=got, ref=ref)
+    return {k: nm(v, ref[k]) for k, v in got.items()}
 
 
 def check_pool_convt_resid(be, B, Ci, Co, H, W, seed=33):
