@@ -16,6 +16,11 @@ CFD_CLIP_FLOATS = 1024  # floats of cfd_fno_params.clip (include/cfdbench_amd.h)
 CFD_STEP_ACCUMULATE = 8   # param = an accumulator laid out like grad: param[i] = fmaf(s, grad[i], param[i]) instead of Adam
 CFD_STEP_ACCUM_INIT = 16  # with CFD_STEP_ACCUMULATE: param[i] = s * grad[i], the previous contents are never read
 CFD_STEP_DECOUPLED_WD = 32  # AdamW: param[i] *= 1 - lr * weight_decay, then Adam on the undecayed gradient (ignored with CFD_STEP_ACCUMULATE)
+# needs grads->clip: a gradient norm that is not finite skips the step -- param and the moments keep their bits, clip[1] = 0 (ignored with
+# CFD_STEP_ACCUMULATE); the clip buffer's last two floats then count the skipped steps
+CFD_STEP_SKIP_NONFINITE = 64
+CFD_CLIP_SKIPPED = CFD_CLIP_FLOATS - 1      # skipped steps since the caller zeroed it
+CFD_CLIP_CONSECUTIVE = CFD_CLIP_FLOATS - 2  # skipped steps since the last applied one
 
 
 class CfdError(RuntimeError):

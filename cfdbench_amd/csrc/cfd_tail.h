@@ -245,9 +245,11 @@ int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp,
 // (same stem_combine_channel, so the same rows), and leaves one fp64 sum of squares per workgroup in clip[2..]; every workgroup of the
 // Adam launch adds those records up in one fixed order and folds coef = min(1, max_grad_norm / (norm + 1e-6)) into the gradient scale.
 // decoupled != 0 (CFD_STEP_DECOUPLED_WD): AdamW -- param *= 1 - lr * weight_decay, then Adam on the undecayed gradient (k_adam_f<VEC, true>).
+// guard != 0 (CFD_STEP_SKIP_NONFINITE; needs clip): a norm that is not finite skips the step -- k_adam_f<VEC, DW, true> returns before it
+// touches param or the moments, clip[1] = 0, and clip[CFD_CLIP_SKIPPED] / clip[CFD_CLIP_CONSECUTIVE] count.
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, int decoupled, void* stream);
+                        float max_grad_norm, int decoupled, int guard, void* stream);
 // CFD_STEP_ACCUMULATE of cfd_fno_adam_step: the same deferred work (`sums`, `job`), but acc[i] = s * grad[i] (init) or fmaf(s, grad[i], acc[i])
 // instead of Adam; `acc` is laid out like `grad` (k_grad_accum, pointwise.hip)
 int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,

@@ -468,6 +468,11 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     // grads->clip / max_grad_norm (ABI 604) are read here and nowhere else: the route does not depend on them
     CFD_REQUIRE(accumulate || !g->clip || g->max_grad_norm > 0.f, CFD_ERR_INVALID_ARG,
                 "cfd_fno_adam_step: grads->max_grad_norm must be > 0 when grads->clip is set (+inf: measure the norm, clip nothing)");
+    // CFD_STEP_SKIP_NONFINITE: the optimiser call skips a step whose gradient norm is not finite.  The norm is the clip buffer's, so the
+    // bit needs it; with CFD_STEP_ACCUMULATE no norm is taken and the bit is ignored (the guard fires later, on the accumulator)
+    const bool guard = !accumulate && (flags & CFD_STEP_SKIP_NONFINITE) != 0;
+    CFD_REQUIRE(!guard || g->clip, CFD_ERR_INVALID_ARG,
+                "cfd_fno_adam_step: CFD_STEP_SKIP_NONFINITE needs grads->clip (max_grad_norm = +inf: guard without clipping)");
     const View v(p, s, 1, act_dtype, ws);
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || !wants_ingrad(g), CFD_ERR_UNSUPPORTED,
                 "cfd_fno_adam_step: grads->d_inputs / d_case_params need fp32 activation storage");
@@ -493,5 +498,5 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
                                     (flags & CFD_STEP_ACCUM_INIT) != 0, stream);
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm,
-                               (flags & CFD_STEP_DECOUPLED_WD) != 0, stream);
+                               (flags & CFD_STEP_DECOUPLED_WD) != 0, guard, stream);
 }

@@ -1864,7 +1864,13 @@ __global__ __launch_bounds__(256) void k_gradsq(float* __restrict__ g, size_t n,
 // the same, still unscaled units as every other gradient) and applies Adam to it; the flat part skips those two ranges.
 // DW: decoupled weight decay (adam_update<true>: the `wd` argument is the factor 1 - lr * weight_decay); a variant of its own, so the
 // code of k_adam_f<VEC, false> is what k_adam_f<VEC> was.
-template <bool VEC, bool DW = false>
+// GUARD (CFD_STEP_SKIP_NONFINITE; the launcher sets it only with clip.buf != NULL): a norm that is not finite -- a NaN or an inf in the
+// gradient, an overflowing sum, an inf or NaN normaliser, a NaN grad_scale -- makes the launch a SKIPPED STEP.  Every workgroup has added
+// up the same records in the same order, so the test is uniform across the grid and each returns before it has loaded an element of
+// p, m or v.  The thread that stores clip[0..1] keeps the two counters at the buffer's end (plain load, add, store: no other thread of the
+// launch and no record of k_gradsq reaches them).  n == 0 is no step at all: the counters stay.  A variant of its own, so the code of
+// k_adam_f<VEC, DW, false> is what k_adam_f<VEC, DW> was.
+template <bool VEC, bool DW = false, bool GUARD = false>
 __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
                                                 float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip) {
@@ -1875,7 +1881,21 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
         const double sq = clip_total_sq(clip.buf, clip.nrec, s_sq);
         const double norm = fabs((double)gscale) * sqrt(sq);
         const double coef = n ? fmin(1.0, (double)clip.max_norm / (norm + 1e-6)) : 1.0;
-        if (blockIdx.x == 0 && threadIdx.x == 0) clip.buf[0] = (float)norm, clip.buf[1] = (float)coef;
+        if constexpr (GUARD) {
+            const bool skip = n && !__builtin_isfinite(norm);  // (the build has no fast-math flag: the test is not folded away)
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                clip.buf[0] = (float)norm, clip.buf[1] = skip ? 0.f : (float)coef;
+                if (skip) {
+                    clip.buf[CFD_CLIP_SKIPPED] += 1.f;
+                    clip.buf[CFD_CLIP_CONSECUTIVE] += 1.f;
+                } else if (n) {
+                    clip.buf[CFD_CLIP_CONSECUTIVE] = 0.f;
+                }
+            }
+            if (skip) return;
+        } else {
+            if (blockIdx.x == 0 && threadIdx.x == 0) clip.buf[0] = (float)norm, clip.buf[1] = (float)coef;
+        }
         gscale *= (float)coef;  // (coef == 1: the same bits as without clipping)
     }
     const int njob = job.part ? job.C : 0;
@@ -1926,8 +1946,9 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
 
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, int decoupled, void* stream) {
+                        float max_grad_norm, int decoupled, int guard, void* stream) {
     CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
+    CFD_REQUIRE(!guard || clip, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_STEP_SKIP_NONFINITE needs grads->clip");
     CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: step must be >= 1");
     CFD_REQUIRE(!clip || max_grad_norm > 0.f, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: max_grad_norm must be > 0 (+inf: measure only)");
     if (n == 0 && !clip) return CFD_OK;
@@ -1940,7 +1961,8 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
     ClipArgs ca{};
     if (clip) {  // the norm needs the finished fc0 rows: k_gradsq takes the job, Adam's launch runs the flat update alone
         const int njob = jb.part ? jb.C : 0;
-        CFD_REQUIRE(2 + 2 * (njob + CFD_CLIP_MAX_WGS) <= CFD_CLIP_FLOATS, CFD_ERR_UNSUPPORTED,
+        // (with the guard the last two floats are its counters: the records must end in front of them)
+        CFD_REQUIRE(2 + 2 * (njob + CFD_CLIP_MAX_WGS) <= CFD_CLIP_FLOATS - (guard ? 2 : 0), CFD_ERR_UNSUPPORTED,
                     "cfd_fno_adam_step: clipping with a lifting layer of %d channels", njob);
         const size_t gsq = n == 0 ? 0 : (blocks < CFD_CLIP_MAX_WGS ? blocks : (size_t)CFD_CLIP_MAX_WGS);
         ca = ClipArgs{clip, max_grad_norm, (int)gsq + njob};
@@ -1959,20 +1981,23 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
     CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
     const dim3 grid((unsigned)blocks), wg(256);
     const float rbc1 = (float)bc1, rbc2 = (float)(1.0 / sqrt(bc2));
-    if (decoupled) {  // AdamW: p *= 1 - lr * wd (the factor in double, rounded once, as torch forms it), then Adam on the undecayed gradient
-        const float decay = (float)(1.0 - (double)lr * (double)weight_decay);
-        if (vec)
-            hipLaunchKernelGGL((k_adam_f<true, true>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                               decay, rbc1, rbc2, grad_scale, sums, jb, ca);
-        else
-            hipLaunchKernelGGL((k_adam_f<false, true>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                               decay, rbc1, rbc2, grad_scale, sums, jb, ca);
-    } else if (vec)
-        hipLaunchKernelGGL((k_adam_f<true, false>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                           weight_decay, rbc1, rbc2, grad_scale, sums, jb, ca);
-    else
-        hipLaunchKernelGGL((k_adam_f<false, false>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                           weight_decay, rbc1, rbc2, grad_scale, sums, jb, ca);
+    // AdamW: p *= 1 - lr * wd (the factor in double, rounded once, as torch forms it), then Adam on the undecayed gradient
+    const float wdarg = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : weight_decay;
+#define CFD_ADAM_F_LAUNCH(VEC_, DW_, GUARD_)                                                                                           \
+    hipLaunchKernelGGL((k_adam_f<VEC_, DW_, GUARD_>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, \
+                       beta2, eps, wdarg, rbc1, rbc2, grad_scale, sums, jb, ca)
+    if (guard) {  // (the variants that can skip the step: clip != NULL was required above)
+        if (decoupled) {
+            if (vec) CFD_ADAM_F_LAUNCH(true, true, true);
+            else CFD_ADAM_F_LAUNCH(false, true, true);
+        } else if (vec) CFD_ADAM_F_LAUNCH(true, false, true);
+        else CFD_ADAM_F_LAUNCH(false, false, true);
+    } else if (decoupled) {
+        if (vec) CFD_ADAM_F_LAUNCH(true, true, false);
+        else CFD_ADAM_F_LAUNCH(false, true, false);
+    } else if (vec) CFD_ADAM_F_LAUNCH(true, false, false);
+    else CFD_ADAM_F_LAUNCH(false, false, false);
+#undef CFD_ADAM_F_LAUNCH
     CFD_LAUNCH_CHECK("cfd_fno_adam_step");
     return CFD_OK;
 }

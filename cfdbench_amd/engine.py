@@ -9,6 +9,9 @@ key names, complex64 spectral weights) always reflects the trained weights and c
 Fine-tuning: parameters with ``requires_grad = False`` (or outside ``trainable=``) stay out of the flat buffers and keep their own storage;
 the backward pass stops behind the phase of the shallowest trainable tensor (``last_backward_phase``).  ``optimizer="adamw"`` runs
 decoupled weight decay inside the same optimiser launch (CFD_STEP_DECOUPLED_WD).
+
+Unattended runs: ``skip_nonfinite=True`` skips an optimiser step whose gradient norm is not finite inside that same launch
+(CFD_STEP_SKIP_NONFINITE): weights and moments keep their bits, the counts stay on the device.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
-from ._capi import CFD_CLIP_FLOATS, CFD_STEP_DECOUPLED_WD
+from ._capi import CFD_CLIP_CONSECUTIVE, CFD_CLIP_FLOATS, CFD_CLIP_SKIPPED, CFD_STEP_DECOUPLED_WD, CFD_STEP_SKIP_NONFINITE
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
@@ -337,7 +340,7 @@ class FnoTrainEngine:
     def __init__(self, model, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
                  overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None,
-                 trainable: Optional[Sequence[str]] = None, optimizer: str = "adam"):
+                 trainable: Optional[Sequence[str]] = None, optimizer: str = "adam", skip_nonfinite: bool = False):
         """``trainable``: state_dict key prefixes (``{"fc1", "fc2"}``, ``{"blocks.3", "fc1", "fc2"}``) of the parameters to train; the
         others are frozen (their ``requires_grad`` is set to match).  None: the engine honours ``requires_grad`` as it finds it.  The
         flat buffers (parameters, gradient, moments, accumulator, what a data-parallel run exchanges) hold the trainable tensors only, and
@@ -351,6 +354,21 @@ class FnoTrainEngine:
         ``torch.nn.utils.clip_grad_norm_`` with norm_type 2, taken of the gradient Adam applies -- after the deferred normaliser, the
         lifting layer's rows and, data-parallel, the all-reduce and its 1 / world).  None: no clipping, the calls of an engine without
         the argument; ``float("inf")``: the norm is measured (``grad_norm()``) and nothing is clipped.  One launch more per step.
+
+        ``skip_nonfinite``: an optimiser step whose gradient norm is not finite -- a NaN or inf anywhere in the gradient, an all-zero
+        label under nMSE, a rollout window that blew up -- is SKIPPED on the device (CFD_STEP_SKIP_NONFINITE of cfd_fno_adam_step, which
+        is then the optimiser call on every route): parameters and both moments keep their bits, no host sync.  The norm is the one
+        clipping takes, so without ``max_grad_norm`` the engine measures it as ``float("inf")`` does (the same one launch more) and
+        clips nothing.  ``skipped_steps()``, ``consecutive_skipped()`` and ``last_step_skipped()`` are device scalars.  The test sits
+        where the gradient is final, so it holds on every route: ``train_step`` / ``optimizer_step`` / ``train_step_graph`` (the
+        optimiser call is outside the replay), frozen subsets and AdamW (bits beside it), and ``apply_accumulated`` -- accumulation
+        groups and rollout windows: a non-finite micro-batch makes the accumulator non-finite and the whole group is dropped.
+        Data-parallel, both the overlapped and the single exchange decide on the REDUCED gradient: the all-reduce hands every rank the
+        same bits (a NaN on one rank is a NaN in every rank's sum), each rank forms the same norm from them with the same 1 / world, so
+        all ranks skip together and the replicas stay identical without a second collective.
+        ``step_count`` advances on a skipped step too: the bias corrections after a skip are those of t, not of the number of applied
+        steps (the one difference from a ``torch.amp.GradScaler`` skip; it keeps the guarded step without skips bitwise the unguarded
+        one).
 
         ``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
         activations a_0 .. a_L are rounded to bf16 when stored -- half the bytes of what the backward pass re-reads -- and the
@@ -415,11 +433,16 @@ class FnoTrainEngine:
         self._graph = None
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.clip = None
-        if self.max_grad_norm is not None:
-            if not self.max_grad_norm > 0.0:  # (NaN fails the comparison too)
-                raise ValueError("max_grad_norm must be > 0 (None: no clipping, float('inf'): measure the norm only)")
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:  # (NaN fails the comparison too)
+            raise ValueError("max_grad_norm must be > 0 (None: no clipping, float('inf'): measure the norm only)")
+        # the guard rides on the norm clipping takes: without a threshold of the caller's it measures (+inf) and clips nothing
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._skip_flag = CFD_STEP_SKIP_NONFINITE if self.skip_nonfinite else 0  # (beside the pass's flags in every optimiser call)
+        self._clip_threshold = float("inf") if (self.skip_nonfinite and self.max_grad_norm is None) else self.max_grad_norm
+        if self._clip_threshold is not None:
+            # (zeroed: with the guard the last two floats are its counters, CFD_CLIP_SKIPPED / CFD_CLIP_CONSECUTIVE)
             self.clip = torch.zeros(CFD_CLIP_FLOATS, dtype=torch.float32, device=self.device)
-            self.gstruct.clip, self.gstruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+            self.gstruct.clip, self.gstruct.max_grad_norm = self.clip.data_ptr(), self._clip_threshold
         # gradient accumulation over micro-batches (accumulate / apply_accumulated): the accumulator, laid out like flat.grad, and its
         # struct exist from the first accumulate() on -- an engine that never accumulates holds no more memory
         self.accum: Optional[Tensor] = None
@@ -544,7 +567,7 @@ class FnoTrainEngine:
             # kept only with fc0 trainable -- fc0's rows)
             self.astruct = _param_struct([base + (p_ - g0) if t else p_ for p_, t in zip(self.flat.ptrs(True), self.flat.trainable)], self.L)
             if self.clip is not None:  # (read where the struct is the `grads` of the optimiser call on the accumulator)
-                self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self.max_grad_norm
+                self.astruct.clip, self.astruct.max_grad_norm = self.clip.data_ptr(), self._clip_threshold
 
     # ---- training through a K-step rollout window ------------------------------------------------------
     def _window_state(self, inputs: Tensor, case_params: Tensor, K: int, full: bool) -> dict:
@@ -679,7 +702,7 @@ class FnoTrainEngine:
         self._grad_in_accum = True
 
     def _step_flags(self, flags: int) -> int:
-        return flags | self._dw_flag
+        return flags | self._dw_flag | self._skip_flag
 
     def optimizer_step(self, grad_scale: float = 1.0):
         self._no_open_group("optimizer_step")
@@ -689,9 +712,10 @@ class FnoTrainEngine:
         # the pass left work to this launch (nMSE normaliser from sums[2:4], the lifting layer's gradient rows), or the step clips: the
         # norm is taken inside cfd_fno_adam_step, which with flags = 0 is cfd_adam_flat otherwise
         adamw = self._dw_flag != 0  # (decoupled decay exists in cfd_fno_adam_step alone: the optimiser call on every route)
+        # (skip_nonfinite holds a clip buffer: the guard exists in cfd_fno_adam_step alone, like clipping)
         if (self.clip is not None or adamw) and inputs is None:
-            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping and AdamW need the pass that produced the gradients "
-                               "(forward_backward / train_step) first")
+            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping, skip_nonfinite and AdamW need the pass that produced the "
+                               "gradients (forward_backward / train_step) first")
         if flags or self.clip is not None or adamw:
             self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
                           inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
@@ -731,6 +755,25 @@ class FnoTrainEngine:
             raise RuntimeError("FnoTrainEngine.clip_coef: the engine was built without max_grad_norm")
         return self.clip[1]
 
+    def _need_guard(self, what: str) -> None:
+        if not self.skip_nonfinite:
+            raise RuntimeError(f"FnoTrainEngine.{what}: the engine was built without skip_nonfinite")
+
+    def skipped_steps(self) -> Tensor:
+        """0-dim device tensor (a view, no sync): the optimiser steps skipped so far, a count held as a float (exact up to 2^24)."""
+        self._need_guard("skipped_steps")
+        return self.clip[CFD_CLIP_SKIPPED]
+
+    def consecutive_skipped(self) -> Tensor:
+        """0-dim device tensor (a view, no sync): the optimiser steps skipped since the last applied one."""
+        self._need_guard("consecutive_skipped")
+        return self.clip[CFD_CLIP_CONSECUTIVE]
+
+    def last_step_skipped(self) -> Tensor:
+        """0-dim device boolean (no sync): whether the last optimiser call applied nothing (``clip_coef() == 0``)."""
+        self._need_guard("last_step_skipped")
+        return self.clip[1] == 0
+
     def train_step(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None) -> Tensor:
         """One optimisation step; returns the device tensor [sum sq err, sum abs err, sum sq label, n] of THIS rank's
         batch (no host sync -- read it with .tolist() only when logging)."""
@@ -747,9 +790,13 @@ class FnoTrainEngine:
     # ---- optimiser state for full-state checkpoints (the reference saves weights only) ------------
     def state_dict(self) -> Dict[str, object]:
         """Adam moments (flat, in ``abi_parameters`` order), step count and learning rate.  The weights themselves live in
-        the model's ``state_dict`` (the flat buffer is what the model's parameters view)."""
-        return dict(exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
-                    step_count=int(self.step_count), lr=float(self.lr), numel=int(self.flat.numel), trainable=list(self.trainable_names))
+        the model's ``state_dict`` (the flat buffer is what the model's parameters view).  With ``skip_nonfinite`` also
+        ``skipped_steps`` as an int (fetched here: saving synchronises anyway); an engine without the guard writes the state it always did."""
+        state = dict(exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
+                     step_count=int(self.step_count), lr=float(self.lr), numel=int(self.flat.numel), trainable=list(self.trainable_names))
+        if self.skip_nonfinite:
+            state["skipped_steps"] = int(self.clip[CFD_CLIP_SKIPPED].item())
+        return state
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
         # (a state from before the key existed is an all-trainable engine's)
@@ -762,6 +809,9 @@ class FnoTrainEngine:
         self.exp_avg_sq.copy_(state["exp_avg_sq"].to(self.device))
         self.step_count = int(state["step_count"])
         self.lr = float(state["lr"])
+        if self.skip_nonfinite:  # (a state without the key -- an unguarded run's -- means 0; the run of consecutive skips starts anew)
+            self.clip[CFD_CLIP_SKIPPED] = float(state.get("skipped_steps", 0))
+            self.clip[CFD_CLIP_CONSECUTIVE] = 0.0
 
     def scores(self) -> Dict[str, float]:
         """{mse, rmse, mae, nmse} of the last step (loss.py:27-35).  Synchronises."""

@@ -31,7 +31,13 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``optimizer`` (adam = the reference's loop, ``weight_decay`` still unused as there | adamw = decoupled decay by ``weight_decay``:
     torch.optim.AdamW on the eager paths, FnoTrainEngine(optimizer="adamw") with --fused 1; not with --graph 1),
     ``init_from`` (a model.pt to load through ``load_ckpt`` before training: fine-tuning from another run's weights; ignored, with a log
-    line, when --resume 1 finds a train_state.pt).
+    line, when --resume 1 finds a train_state.pt),
+    ``skip_nonfinite`` (1: an optimiser step whose gradient norm is NaN or inf is skipped instead of applied -- --fused 1: on the device,
+    inside the engine's optimiser call, no host sync (FnoTrainEngine(skip_nonfinite=True)); eager paths: the norm of
+    torch.nn.utils.clip_grad_norm_ is tested on the host, ONE HOST SYNC PER OPTIMISER STEP; the log line and train_state.pt carry the
+    skipped count; not with --graph 1; a run resumed with the other value just continues, the count from the state),
+    ``max_consecutive_skips`` (with --skip_nonfinite 1: abort with a RuntimeError once that many optimiser steps in a row were skipped --
+    checked at the log interval on the fused path, per step on the eager ones; the last good checkpoint stays; 0 = never abort).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -63,6 +69,7 @@ _FLAGS: Dict[str, Any] = dict(
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
     fused_accumulation_steps=1, unroll_detach=0, freeze="", train_only="", optimizer="adam", init_from="",
+    skip_nonfinite=0, max_consecutive_skips=100,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -142,6 +149,10 @@ def is_args_valid(args: Args) -> None:
     assert args.optimizer in ("adam", "adamw"), "--optimizer is adam (weight_decay unused, as in the reference) or adamw (decoupled decay)"
     if args.graph:
         assert args.optimizer == "adam", "--graph 1 with --optimizer adamw is not built: cfd_adam_multi has no decoupled form"
+    assert args.skip_nonfinite in (0, 1), "--skip_nonfinite is 0 (apply every step, the reference's loop) or 1 (skip non-finite steps)"
+    assert args.max_consecutive_skips >= 0, "--max_consecutive_skips counts skipped optimiser steps in a row (0 = never abort)"
+    if args.graph:
+        assert not args.skip_nonfinite, "--graph 1 with --skip_nonfinite 1 is not built: cfd_adam_multi has no flags to carry the guard"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

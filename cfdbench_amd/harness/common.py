@@ -100,6 +100,40 @@ def make_optimizer(params, kind: str, lr, weight_decay: float = 0.0, **kw):
     raise ValueError("optimizer must be 'adam' or 'adamw'")
 
 
+class SkipGuard:
+    """--skip_nonfinite / --max_consecutive_skips: the count of skipped optimiser steps and the rule that ends a hopeless run, for every
+    trainer.  The eager paths decide on the host (``eager_step``: one sync per optimiser step); the fused engine decides on the device
+    and hands its counters over where the loop reads device scalars anyway (``check``)."""
+
+    def __init__(self, enabled: bool = False, max_consecutive: int = 100, skipped: int = 0):
+        self.enabled, self.max_consecutive = bool(enabled), int(max_consecutive)
+        self.skipped, self.consecutive = int(skipped), 0
+
+    def check(self, consecutive: int, ep: int, step: int, skipped: Optional[int] = None) -> None:
+        """RuntimeError once ``max_consecutive`` (> 0) optimiser steps in a row were skipped: a run that silently skips everything is
+        worse than one that stops.  Raised before anything is written: the last good checkpoint stays in place."""
+        if skipped is not None:
+            self.skipped = int(skipped)
+        self.consecutive = int(consecutive)
+        if self.enabled and 0 < self.max_consecutive <= self.consecutive:
+            raise RuntimeError(f"--skip_nonfinite: {self.consecutive} optimiser steps in a row had a non-finite gradient norm "
+                               f"(epoch {ep}, step {step}; {self.skipped} skipped in all; --max_consecutive_skips "
+                               f"{self.max_consecutive}): the run is not training any more")
+
+    def eager_step(self, params, optimizer, max_grad_norm: float, ep: int, step: int):
+        """The optimiser step of an eager path behind backward and the gradient exchange: norm = clip_grad_norm_(params, max_grad_norm
+        or inf) -- ``.item()`` on it is the one host sync per step this option costs here -- and ``optimizer.step()`` only when it is
+        finite.  Returns (norm, applied)."""
+        norm = torch.nn.utils.clip_grad_norm_(params, float(max_grad_norm) if float(max_grad_norm) > 0.0 else float("inf"))
+        if bool(torch.isfinite(norm).item()):
+            optimizer.step()
+            self.consecutive = 0
+            return norm, True
+        self.skipped += 1
+        self.check(self.consecutive + 1, ep, step)
+        return norm, False
+
+
 def load_best_ckpt(model, output_dir: Path) -> Path:  # common.py:278-284
     print(f"Finding the best checkpoint from {output_dir}")
     best = get_best_ckpt(output_dir)

@@ -28,7 +28,7 @@ from ..models.deeponet import DeepONet
 from ..models.ffn import FfnModel
 from ..models.loss import loss_name_to_fn
 from .args import Args, is_args_valid
-from .common import (apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot_loss,
+from .common import (SkipGuard, apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot_loss,
                      plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
@@ -102,7 +102,7 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
           lr_scheduler_kind: str = "step", lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5,
           early_stopping_patience: int = 0, early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1,
           graph: bool = False, max_grad_norm: float = 0.0, optimizer_kind: str = "adam", weight_decay: float = 0.0,
-          init_from: str = ""):
+          init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100):
     """src/train.py:148-253: fwd -> ``loss["nmse"].backward()`` -> Adam -> zero_grad; StepLR per epoch.
     ``optimizer_kind`` / ``weight_decay`` / ``init_from`` and the model's ``requires_grad`` flags (--freeze / --train_only): as
     harness/train_auto.py:train.
@@ -111,7 +111,9 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
     ``early_stopping_patience`` / ``gradient_accumulation_steps``: the same options, with the same semantics, as
     harness/train_auto.py:train (harness/schedule.py); the defaults are the reference's loop.  ``max_grad_norm`` > 0:
     ``torch.nn.utils.clip_grad_norm_`` before every optimiser step (after the gradient exchange; not with ``graph``); the log line
-    then carries ``grad_norm``."""
+    then carries ``grad_norm``.  ``skip_nonfinite`` / ``max_consecutive_skips``: an optimiser step whose gradient norm is not finite is
+    skipped, ``common.SkipGuard.eager_step`` (one host sync per optimiser step; not with ``graph``); its micro-batches' losses stay out of
+    the loss history, the log line and train_state.pt carry ``skipped``."""
     rank, world = _rank_world()
     output_dir = Path(output_dir)
     clip = float(max_grad_norm) > 0.0
@@ -119,6 +121,9 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
         raise ValueError("max_grad_norm must be >= 0 (0 = no clipping)")
     if clip and graph:
         raise NotImplementedError("--max_grad_norm needs --graph 0: the captured multi-tensor Adam step has no clipping")
+    if skip_nonfinite and graph:
+        raise NotImplementedError("--skip_nonfinite needs --graph 0: cfd_adam_multi has no flags to carry the guard")
+    guard = SkipGuard(skip_nonfinite, max_consecutive_skips)
     if world > 1:
         broadcast_model_state(model)
 
@@ -176,6 +181,7 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
         if state.get("early_stopping") is not None:
             stopper.load_state_dict(state["early_stopping"])
         start_ep, global_step, all_train_losses = state["ep"] + 1, state["global_step"], list(state["train_losses"])
+        guard.skipped = int(state.get("skipped_steps", 0))  # (a state written without the option: 0)
         torch.set_rng_state(state["rng"])
         if rank == 0:
             print(f"resuming after epoch {state['ep']} (step {global_step}) from {state_path}")
@@ -209,20 +215,29 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
             loss = model(**batch)["loss"]["nmse"]
             group = accum if step < n_full else n_steps - n_full  # the epoch's trailing group may be shorter
             (loss / group if group > 1 else loss).backward()
+            applied = True
             if (step + 1) % accum == 0 or step + 1 == n_steps:
                 if world > 1:
                     sync_gradients(list(model.parameters()))
-                if clip:
-                    grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
-                optimizer.step()
+                if guard.enabled:  # (the gradients are the same on every rank behind the exchange: all ranks skip together)
+                    grad_norm, applied = guard.eager_step(model.parameters(), optimizer, max_grad_norm, ep, step)
+                else:
+                    if clip:
+                        grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
+                    optimizer.step()
                 optimizer.zero_grad()
-            ep_train_losses.append(loss.item())  # src/train.py:203
+            if applied:
+                ep_train_losses.append(loss.item())  # src/train.py:203
+            else:  # the loss history averages applied steps only: the skipped group's earlier micro-batches leave it, this one never enters
+                del ep_train_losses[len(ep_train_losses) - (step % accum):]
             global_step += 1
             if global_step % log_interval == 0 and not measure_time and rank == 0:
                 avg_loss = sum(ep_train_losses) / (len(ep_train_losses) + 1e-5)
                 line = dict(ep=ep, step=step, loss=f"{avg_loss:.3e}", lr=f"{schedule.lr:.3e}")
                 if clip:
                     line["grad_norm"] = "nan" if grad_norm is None else f"{float(grad_norm):.3e}"
+                if guard.enabled:
+                    line["skipped"] = guard.skipped
                 line["time"] = round(time.time() - start_time)
                 print(line)
         if graph:
@@ -252,7 +267,8 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
             tmp = output_dir / "train_state.pt.tmp"
             torch.save(dict(format=2, ep=ep, global_step=global_step, train_losses=all_train_losses + ep_train_losses,
                             ckpt=ckpt_dir.name, optimizer=optimizer.state_dict(), scheduler=schedule.state_dict(),
-                            early_stopping=stopper.state_dict(), rng=torch.get_rng_state(), world=world), tmp)
+                            early_stopping=stopper.state_dict(), rng=torch.get_rng_state(), world=world,
+                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {})), tmp)
             tmp.replace(state_path)
         if world > 1:  # every rank follows rank 0's validation-driven decisions (plateau rate, early stop)
             flags = torch.tensor([schedule.lr, float(stop)], dtype=torch.float64, device="cuda" if torch.cuda.is_available() else "cpu")
@@ -348,7 +364,7 @@ def main(argv=None):
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
               graph=bool(args.graph), max_grad_norm=args.max_grad_norm, optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
-              init_from=args.init_from)
+              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips)
     if "test" in args.mode and rank == 0:
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

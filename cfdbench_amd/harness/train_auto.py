@@ -34,7 +34,7 @@ from ..models.fno.fno2d import Fno2d
 from ..unroll import collate_windows, unroll_windows, unrolled_loss
 from .args import Args, is_args_valid
 from .autoregressive import init_model
-from .common import (apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
+from .common import (SkipGuard, apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
                      plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
@@ -181,7 +181,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5, early_stopping_patience: int = 0,
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
           unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False, optimizer_kind: str = "adam",
-          weight_decay: float = 0.0, init_from: str = ""):
+          weight_decay: float = 0.0, init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     Fine-tuning: the model's ``requires_grad`` flags are honoured on every path (``common.apply_trainable``: --freeze / --train_only set
@@ -215,6 +215,16 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     ``unroll_steps`` included): ``torch.nn.utils.clip_grad_norm_`` after the gradient exchange, at the accumulation group's boundary.
     Not with ``graph``.  The rank-0 log line then carries ``grad_norm`` (the norm before clipping, of the last optimiser step).
 
+    ``skip_nonfinite``: an optimiser step whose gradient norm is NaN or inf -- a bad frame, an all-zero label under nmse, a window that
+    blew up -- is skipped.  ``fused``: on the device, inside the engine's optimiser call (FnoTrainEngine(skip_nonfinite=True)), no host
+    sync; an accumulation group or window with one bad micro-batch is dropped whole; data-parallel, all ranks skip together.  Eager
+    paths: ``common.SkipGuard.eager_step`` -- the norm of ``clip_grad_norm_`` is tested on the host, one sync per optimiser step.  The
+    losses of skipped steps stay out of the loss history (fused: masked with ``last_step_skipped()`` on the device and dropped where the
+    epoch's losses are fetched), the log line carries ``skipped`` and -- fused -- ``nmse_applied``, the mean over the applied steps since
+    the last log line of this epoch; train_state.pt carries ``skipped_steps``.  ``max_consecutive_skips`` = N > 0: RuntimeError once N
+    optimiser steps in a row were skipped -- fused: checked at the log interval, where the loop reads device scalars anyway, on every
+    rank; eager: at the step.  Nothing is written then: the last good checkpoint stays.  Not with ``graph``.
+
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
     other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop.
     ``gradient_accumulation_steps`` = N > 1 with ``fused``: FnoTrainEngine.accumulate per micro-batch (weight 1 / group) and
@@ -227,6 +237,9 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         raise ValueError("max_grad_norm must be >= 0 (0 = no clipping)")
     if clip and graph:
         raise NotImplementedError("--max_grad_norm needs --graph 0: the captured multi-tensor Adam step has no clipping")
+    if skip_nonfinite and graph:
+        raise NotImplementedError("--skip_nonfinite needs --graph 0: cfd_adam_multi has no flags to carry the guard")
+    guard = SkipGuard(skip_nonfinite, max_consecutive_skips)
     unroll = int(unroll_steps)
     detach = bool(unroll_detach)
     if detach and unroll <= 1:
@@ -305,7 +318,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             raise NotImplementedError("--fused 1 needs the fno model")
         # (adam: weight_decay stays unused, as in the reference)
         engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None,
-                                optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0)
+                                optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0,
+                                skip_nonfinite=guard.enabled)
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -357,6 +371,9 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         if state.get("early_stopping") is not None:
             stopper.load_state_dict(state["early_stopping"])
         start_ep, global_step, train_losses = state["ep"] + 1, state["global_step"], list(state["train_losses"])
+        # (a run resumed with the other --skip_nonfinite value just continues: a state without the count means 0; the fused engine took
+        # its counter from the optimiser state above)
+        guard.skipped = int(state.get("skipped_steps", 0))
         torch.set_rng_state(state["rng"])  # the DataLoader draws its shuffles from the host generator
         if rank == 0:
             print(f"resuming after epoch {state['ep']} (step {global_step}) from {state_path}")
@@ -364,6 +381,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         ep_start_time = time.time()
         cur_lr = schedule.lr
         ep_train_losses: List = []
+        ep_skipped: List = []  # fused --skip_nonfinite: per loss entry, whether its optimiser step was skipped (device booleans)
+        logged = 0  # loss entries that earlier log lines of this epoch have averaged
         model.train()
         if world > 1 and ep > 0:
             train_loader = make_loader(ep)
@@ -391,6 +410,9 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                     ep_train_losses.append((wsums[:, 0] / wsums[:, 2]).mean())
                 else:
                     ep_train_losses.append((sums[0] / sums[2]).clone())
+                if guard.enabled and ((step + 1) % accum == 0 or step + 1 == n_steps):
+                    # behind an optimiser call: its verdict (a device boolean, no sync) for every loss entry of its group
+                    ep_skipped += [engine.last_step_skipped()] * (len(ep_train_losses) - len(ep_skipped))
                 loss_mse = loss_nmse = None
             elif graph:
                 from ..graph import GraphedTrainStep
@@ -431,16 +453,26 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 # mean over the micro-batches of THIS group: the trailing group of an epoch may be shorter than `accum`
                 group = accum if step < n_full else n_steps - n_full
                 (loss["nmse"] / group if group > 1 else loss["nmse"]).backward()  # train_auto.py:255
+                applied = True
                 if (step + 1) % accum == 0 or step + 1 == n_steps:
                     if world > 1:
                         sync_gradients(list(model.parameters()))  # one flat all-reduce, DDP semantics
-                    if clip:
-                        grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
-                    optimizer.step()
+                    if guard.enabled:  # (the gradients are the same on every rank behind the exchange: all ranks skip together)
+                        grad_norm, applied = guard.eager_step(model.parameters(), optimizer, max_grad_norm, ep, step)
+                    else:
+                        if clip:
+                            grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
+                        optimizer.step()
                     optimizer.zero_grad()
-                ep_train_losses.append(loss["nmse"].item())  # train_auto.py:260
+                if applied:
+                    ep_train_losses.append(loss["nmse"].item())  # train_auto.py:260
+                else:  # the loss history averages applied steps only: the skipped group's earlier micro-batches leave it
+                    del ep_train_losses[len(ep_train_losses) - (step % accum):]
                 loss_mse, loss_nmse = loss["mse"], loss["nmse"]
             global_step += 1
+            if guard.enabled and engine is not None and global_step % log_interval == 0:
+                # a hopeless run ends here, on every rank (they skip together), before the log line and long before the next checkpoint
+                guard.check(int(engine.consecutive_skipped()), ep, step, skipped=int(engine.skipped_steps()))
             if global_step % log_interval == 0 and rank == 0:
                 if engine is not None and windows is not None:  # (the log line's mse: the last step's, as on the eager path)
                     rows = wsums.tolist()
@@ -454,10 +486,21 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 if clip:  # (fetched here only, where the loss has synchronised already)
                     gn = engine.grad_norm() if engine is not None else grad_norm
                     line["grad_norm"] = "nan" if gn is None else f"{float(gn):.3e}"
+                if guard.enabled:
+                    if engine is not None and len(ep_skipped) > logged:  # the interval's training loss over the applied steps alone
+                        done = len(ep_skipped)  # (entries of a group still open have no verdict yet: the next line takes them)
+                        vals = torch.stack(ep_train_losses[logged:done])[~torch.stack(ep_skipped[logged:done])]
+                        line["nmse_applied"] = f"{float(vals.mean()):.3e}" if vals.numel() else "nan"
+                        logged = done
+                    line["skipped"] = guard.skipped
                 line["time"] = round(time.time() - start_time)
                 print(line)
         if engine is not None or graph:
             ep_train_losses = torch.stack(ep_train_losses).tolist() if ep_train_losses else []
+            if ep_skipped:  # (an epoch ends with its last group applied or skipped: one verdict per entry)
+                ep_train_losses = [v for v, s in zip(ep_train_losses, torch.stack(ep_skipped).tolist()) if not s]
+        if guard.enabled and engine is not None:
+            guard.skipped = int(engine.skipped_steps())  # (behind the epoch's fetch: no sync of its own)
         schedule.epoch_end()
         if measure_time:
             print("Time usage:", time.time() - ep_start_time)
@@ -494,7 +537,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             torch.save(dict(format=2, ep=ep, global_step=global_step, train_losses=train_losses, ckpt=ckpt_dir.name,
                             optimizer=opt_state, scheduler=schedule.state_dict(), early_stopping=stopper.state_dict(),
                             rng=torch.get_rng_state(), fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach),
-                            model_extra=model.extra_train_state() if hasattr(model, "extra_train_state") else None), tmp)
+                            model_extra=model.extra_train_state() if hasattr(model, "extra_train_state") else None,
+                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {})), tmp)
             tmp.replace(state_path)
         else:
             stop = False
@@ -552,7 +596,7 @@ def main(argv=None):
               gradient_accumulation_steps=args.fused_accumulation_steps if args.fused else args.gradient_accumulation_steps,
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
               unroll_detach=bool(args.unroll_detach), optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
-              init_from=args.init_from)
+              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips)
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         load_best_ckpt(model, output_dir)

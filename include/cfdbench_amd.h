@@ -526,11 +526,15 @@ typedef struct { /* device pointers, reference state_dict order (SURVEY.md 8b "C
      *   written itself, so the buffer needs no initialisation.
      * max_grad_norm: read when clip != NULL; > 0, +inf allowed (= measure the norm, clip nothing).  <= 0 or NaN: CFD_ERR_INVALID_ARG
      *   before any launch.  n == 0: clip[0] = 0, clip[1] = 1.  A non-finite norm is reported in clip[0] and does not fault; nothing more
-     *   is promised (torch without error_if_nonfinite). */
+     *   is promised (torch without error_if_nonfinite) -- unless the call carries CFD_STEP_SKIP_NONFINITE (below), which makes such a
+     *   call a skipped step and keeps two counters in the buffer's last two floats. */
     float* clip;
     float max_grad_norm;
 } cfd_fno_params;
 #define CFD_CLIP_FLOATS 1024 /* 2 + two floats per partial record: 256 workgroups of the flat sum + one per lifting-layer row (<= 255) */
+/* With CFD_STEP_SKIP_NONFINITE only (without the bit these two floats are scratch like the rest, neither read nor written): */
+#define CFD_CLIP_SKIPPED (CFD_CLIP_FLOATS - 1)     /* skipped steps since the caller zeroed it */
+#define CFD_CLIP_CONSECUTIVE (CFD_CLIP_FLOATS - 2) /* skipped steps since the last applied one */
 
 /* Bytes of caller-provided workspace: activations kept for backward + scratch.  training=0: forward only.   */
 size_t cfd_fno_workspace_bytes(const cfd_plan* plan, const cfd_fno_shape* shape, int training);
@@ -622,13 +626,41 @@ int cfd_fno_backward_phase_ex(const cfd_plan* plan, const cfd_fno_shape* shape, 
  *                          are without the bit.  weight_decay == 0 with the bit: the bits of plain Adam.  Together with
  *                          CFD_STEP_ACCUMULATE the bit is IGNORED: no hyper-parameter is read there; pass it with the optimiser call on
  *                          the accumulator.  Without the bit the call is what it was before the bit existed, bit for bit (coupled L2
- *                          decay: weight_decay * param is added to the gradient).  No launch more than Adam.                          */
+ *                          decay: weight_decay * param is added to the gradient).  No launch more than Adam.
+ *
+ * Skipping non-finite steps on the device (FnoTrainEngine(skip_nonfinite=True)) -- one more bit of cfd_fno_adam_step's `flags`, which the
+ * forward call and the backward phases never see either:
+ *   CFD_STEP_SKIP_NONFINITE  needs grads->clip (NULL: CFD_ERR_INVALID_ARG before any launch; max_grad_norm = +inf: measure and guard, clip
+ *                          nothing; a finite threshold clips as without the bit whenever the norm is finite).  With `norm` as defined at
+ *                          cfd_fno_params.clip -- |s| * sqrt(sum_i grad[i]^2), formed in fp64 -- a norm that is NOT FINITE makes the call
+ *                          a SKIPPED STEP: a NaN or +-inf anywhere in the flat gradient, a sum of squares that overflows, an inf or NaN
+ *                          normaliser sums[3] / sums[2] (an all-zero label under nMSE), a NaN grad_scale.  One definition; the loss sums
+ *                          are not tested on their own.  A skipped step:
+ *                            - writes neither param nor exp_avg nor exp_avg_sq (they keep their bits, and are not even loaded);
+ *                            - leaves the gradient buffer as the pass left it; under CFD_TRAIN_DEFER_STEM the fc0 rows are still
+ *                              finished into it, as with clipping;
+ *                            - stores clip[0] = the non-finite norm and clip[1] = 0 (nothing was applied).
+ *                          Counters: while the bit is used, clip[CFD_CLIP_SKIPPED] and clip[CFD_CLIP_CONSECUTIVE] -- the buffer's last two
+ *                          floats -- persist across calls; the caller zeroes them once.  A skipped call adds 1 to both, an applied call
+ *                          with the bit stores 0 to the consecutive one.  Counts as floats, exact up to 2^24, kept by the one thread that
+ *                          stores clip[0..1], no atomics.  The partial records must end in front of them: a lifting-layer job of more
+ *                          than 254 rows together with the bit is CFD_ERR_UNSUPPORTED (no admitted shape comes close).  n == 0: as
+ *                          without the bit, clip[0] = 0, clip[1] = 1, counters untouched.
+ *                          STEP COUNT: `step` is the caller's, by value, and the caller advances it on a skipped step too, so the bias
+ *                          corrections after a skip are those of t, not of t - skipped.  This is the one difference from a
+ *                          torch.amp.GradScaler skip and it is deliberate: a device-side t would have to form the bias corrections on
+ *                          the device, and the guarded call without skips would lose what it has now -- with a finite norm, parameters,
+ *                          moments, gradient buffer and clip[0..1] are bitwise those of the call without the bit.
+ *                          Together with CFD_STEP_ACCUMULATE the bit is IGNORED: no norm is taken there, a non-finite micro-batch makes
+ *                          the accumulator non-finite, and the optimiser call on the accumulator with the bit skips the whole group.
+ *                          No launch more than clipping costs (k_gradsq).                                                             */
 #define CFD_TRAIN_DEFER_SCALE 1
 #define CFD_TRAIN_DEFER_HEAD 2
 #define CFD_TRAIN_DEFER_STEM 4
 #define CFD_STEP_ACCUMULATE 8   /* cfd_fno_adam_step only */
 #define CFD_STEP_ACCUM_INIT 16  /* only together with CFD_STEP_ACCUMULATE */
 #define CFD_STEP_DECOUPLED_WD 32  /* cfd_fno_adam_step only; ignored with CFD_STEP_ACCUMULATE */
+#define CFD_STEP_SKIP_NONFINITE 64  /* cfd_fno_adam_step only; ignored with CFD_STEP_ACCUMULATE */
 int cfd_fno_forward_train_f(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params,
                             const cfd_fno_params* grads, const float* inputs, const float* case_params, const float* mask,
                             const float* label, float* preds, float* sums, float* coef, void* ws, int which, float upstream,
