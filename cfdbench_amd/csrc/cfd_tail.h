@@ -238,11 +238,11 @@ int cfd_int_stemg_splits(const cfd_plan* p, int B);
 int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp, float* gw, float* gb, int B, int C, int in_chan, int P,
                           void* stream);
 
-// Adam on the flat parameter buffer with the deferred work of the fused training step (fno.cpp: cfd_fno_adam_step): `sums` != NULL:
+// optim.hip: Adam on the flat parameter buffer with the deferred work of the fused training step (fno.cpp: cfd_fno_adam_step): `sums` != NULL:
 // every gradient is multiplied by sums[3] / sums[2] on top of grad_scale (deferred nMSE normaliser); job.part != NULL: workgroup c < C
 // finishes the lifting layer's gradient row c from the block kernel's sum records, stores it and applies Adam to it.
 // clip != NULL (cfd_fno_params.clip, ABI 604): global gradient-norm clipping.  One launch more: k_gradsq takes the lifting layer's job over
-// (same stem_combine_channel, so the same rows), and leaves one fp64 sum of squares per workgroup in clip[2..]; every workgroup of the
+// (the same stem_row, so the same rows), and leaves one fp64 sum of squares per workgroup in clip[2..]; every workgroup of the
 // Adam launch adds those records up in one fixed order and folds coef = min(1, max_grad_norm / (norm + 1e-6)) into the gradient scale.
 // decoupled != 0 (CFD_STEP_DECOUPLED_WD): AdamW -- param *= 1 - lr * weight_decay, then Adam on the undecayed gradient (k_adam_f<VEC, true>).
 // guard != 0 (CFD_STEP_SKIP_NONFINITE; needs clip): a norm that is not finite skips the step -- k_adam_f<VEC, DW, true> returns before it
@@ -251,6 +251,6 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
                         float max_grad_norm, int decoupled, int guard, void* stream);
 // CFD_STEP_ACCUMULATE of cfd_fno_adam_step: the same deferred work (`sums`, `job`), but acc[i] = s * grad[i] (init) or fmaf(s, grad[i], acc[i])
-// instead of Adam; `acc` is laid out like `grad` (k_grad_accum, pointwise.hip)
+// instead of Adam (the same stem_row and flat_walk, AccumOp for AdamOp); `acc` is laid out like `grad` (k_grad_accum)
 int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,
                          void* stream);

@@ -1,8 +1,7 @@
-// Channel-mixing (1x1 conv) kernels, the Fno2d input stem, MseLoss reductions and the flat Adam step.
+// Channel-mixing (1x1 conv) kernels, the Fno2d input stem, MseLoss reductions, GELU / dropout (the optimiser launches: optim.hip).
 //   nn.Conv2d(k=1)            src/models/fno/fno2d.py:104,150      -> k_chanmix / k_chan_wgrad
 //   feature assembly + fc0    src/models/fno/fno2d.py:189-217      -> k_stem_fwd / k_chan_wgrad<STEM>
 //   MseLoss                   src/models/loss.py:22-37             -> k_loss_part / k_loss_final
-//   torch.optim.Adam          src/train_auto.py:213,256            -> k_adam
 #include "cfd_common.h"
 #include "cfd_tail.h"
 
@@ -1709,554 +1708,5 @@ extern "C" int cfd_gelu_bwd(const float* x, const float* gy, float* gx, size_t n
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL((k_gelu<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, gy, gx, n);
     CFD_LAUNCH_CHECK("cfd_gelu_bwd");
-    return CFD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Adam  (torch.optim.Adam defaults: amsgrad=False, maximize=False; train_auto.py:213)
-// ------------------------------------------------------------------------------------------------------
-// DW (CFD_STEP_DECOUPLED_WD of cfd_fno_adam_step; torch.optim.AdamW's single-tensor path): `wd` carries the factor 1 - lr * weight_decay
-// (formed on the host in double, rounded to fp32) and the parameter is multiplied by it before the update; the gradient stays undecayed.
-// The product and the scaled gradient are made opaque so that each is rounded on its own and what follows contracts exactly as it does
-// without DW: a factor of 1 (weight_decay = 0) then gives the bits of plain Adam, with any gradient scale.  The instantiations without DW
-// are the code they were before DW existed.
-template <bool DW = false>
-__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float wd,
-                                            float bc1, float rsqrt_bc2, float gscale) {
-    float gi = g * gscale;
-    if constexpr (DW) {
-        gi = cfd_opaque_f(gi);  // (rounded on its own, as the select on wd below leaves it: not contracted into gi - m)
-        p = cfd_opaque_f(p * wd);
-    } else {
-        if (wd != 0.f) gi = fmaf(wd, p, gi);
-    }
-    m = fmaf(1.f - b1, gi - m, m);                 // m.lerp_(g, 1-b1)
-    v = fmaf(b2, v, (1.f - b2) * gi * gi);         // v.mul_(b2).addcmul_(g, g, 1-b2)
-    const float denom = sqrtf(v) * rsqrt_bc2 + eps;  // sqrt(v)/sqrt(bc2) + eps
-    p = p - (lr / bc1) * (m / denom);
-}
-// VEC: the four buffers are 16-byte aligned -- a thread owns four consecutive elements per trip (one 16-byte load per buffer: the
-// flat buffer of the FNO engine, 926 k elements, is ONE trip of 905 workgroups instead of two trips of 2048); the last n % 4 elements
-// go to the first threads of the grid one by one.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                              float wd, float bc1, float rsqrt_bc2, float gscale) {
-    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
-    if constexpr (VEC) {
-        const size_t n4 = n >> 2;
-        for (size_t i = t0; i < n4; i += nt) {
-            f32x4 pi = reinterpret_cast<const f32x4*>(p)[i], mi = reinterpret_cast<const f32x4*>(m)[i], vi = reinterpret_cast<const f32x4*>(v)[i];
-            const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float pj = pi[j], mj = mi[j], vj = vi[j];
-                adam_update(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-                pi[j] = pj, mi[j] = mj, vi[j] = vj;
-            }
-            reinterpret_cast<f32x4*>(m)[i] = mi;
-            reinterpret_cast<f32x4*>(v)[i] = vi;
-            reinterpret_cast<f32x4*>(p)[i] = pi;
-        }
-        for (size_t i = 4 * n4 + t0; i < n; i += nt) adam_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-    } else {
-        for (size_t i = t0; i < n; i += nt) adam_update(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Global gradient-norm clipping of the fused training step (cfd_fno_params.clip, ABI 604; torch.nn.utils.clip_grad_norm_, norm_type 2).
-// The gradient is final only inside the optimiser launch (CFD_TRAIN_DEFER_*: the nMSE normaliser is a factor Adam applies, the fc0 rows
-// are finished by Adam's workgroups), so the norm is taken there: k_gradsq carries the lifting layer's job instead of k_adam_f and sums
-// squares in fp64, one record per workgroup; k_adam_f adds the records up (every workgroup the same few hundred doubles in the same
-// order, so the same coefficient) and multiplies it into the gradient scale.  No atomics: two calls give the same bits.
-// ------------------------------------------------------------------------------------------------------
-// (a record is an fp64 stored as two 32-bit words: the clip buffer is a float buffer on any 4-byte boundary)
-__device__ __forceinline__ void clip_store_f64(float* q, double d) {
-    unsigned long long u;
-    __builtin_memcpy(&u, &d, 8);
-    const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-    __builtin_memcpy(q, &lo, 4);
-    __builtin_memcpy(q + 1, &hi, 4);
-}
-__device__ __forceinline__ double clip_load_f64(const float* q) {
-    unsigned lo, hi;
-    __builtin_memcpy(&lo, q, 4);
-    __builtin_memcpy(&hi, q + 1, 4);
-    const unsigned long long u = ((unsigned long long)hi << 32) | lo;
-    double d;
-    __builtin_memcpy(&d, &u, 8);
-    return d;
-}
-// sum over the 256 threads of a workgroup, fixed tree; every thread calls it and gets the total
-__device__ __forceinline__ double clip_block_sum(double a, double (&s_sq)[256]) {
-    s_sq[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = 128; h >= 1; h >>= 1) {
-        if ((int)threadIdx.x < h) s_sq[threadIdx.x] += s_sq[threadIdx.x + h];
-        __syncthreads();
-    }
-    return s_sq[0];
-}
-__device__ __forceinline__ double clip_total_sq(const float* __restrict__ buf, int nrec, double (&s_sq)[256]) {
-    double a = 0.0;
-    for (int r = threadIdx.x; r < nrec; r += 256) a += clip_load_f64(buf + 2 + 2 * r);
-    return clip_block_sum(a, s_sq);
-}
-
-// Workgroup c < job.C: row c of the lifting layer's gradient (what k_adam_f's workgroup c does without clipping, minus Adam) and the sum
-// of its squares; the other workgroups: the squares of the flat gradient buffer outside the lifting layer's two ranges, thread-strided,
-// four independent loads per thread and trip.  Record blockIdx.x of clip[2..] = this workgroup's sum.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_gradsq(float* __restrict__ g, size_t n, float* __restrict__ clip, const StemAdamJob job) {
-    __shared__ float s_r[CFD_STEMG_NA][256];
-    __shared__ double s_sq[256];
-    const int njob = job.part ? job.C : 0;
-    const int F = job.in_chan + 3 + job.P;
-    double acc = 0.0;
-    if ((int)blockIdx.x < njob) {
-        const int c = blockIdx.x;
-        stem_combine_channel(job.part, job.nrec, job.spl, job.cp, job.P, job.C, c, s_r);
-        if ((int)threadIdx.x <= F) {
-            const bool bias = (int)threadIdx.x == F;
-            const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
-            g[bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x] = gv;
-            acc = (double)gv * gv;
-        }
-    } else {
-        const size_t jw0 = (size_t)job.w_off, jw1 = jw0 + (size_t)job.C * F, jb0 = (size_t)job.b_off, jb1 = jb0 + job.C;
-        auto mine = [&](size_t e) { return !(njob && ((e >= jw0 && e < jw1) || (e >= jb0 && e < jb1))); };
-        const size_t t0 = (size_t)(blockIdx.x - njob) * blockDim.x + threadIdx.x, nt = (size_t)(gridDim.x - njob) * blockDim.x;
-        if constexpr (VEC) {
-            const size_t n4 = n >> 2;
-            const size_t jlo = jw0 < jb0 ? jw0 : jb0, jhi = jw1 > jb1 ? jw1 : jb1;
-            for (size_t i0 = t0; i0 < n4; i0 += 4 * nt) {
-                f32x4 x[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const size_t i = i0 + u * nt;
-                    x[u] = i < n4 ? reinterpret_cast<const f32x4*>(g)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const size_t i = i0 + u * nt;
-                    const bool edge = njob && 4 * i < jhi && 4 * i + 4 > jlo;  // a unit that touches the lifting layer's ranges
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (!edge || mine(4 * i + j)) acc += (double)x[u][j] * x[u][j];
-                }
-            }
-            for (size_t i = 4 * n4 + t0; i < n; i += nt)
-                if (mine(i)) acc += (double)g[i] * g[i];
-        } else {
-            for (size_t i = t0; i < n; i += nt)
-                if (mine(i)) acc += (double)g[i] * g[i];
-        }
-    }
-    const double tot = clip_block_sum(acc, s_sq);
-    if (threadIdx.x == 0) clip_store_f64(clip + 2 + 2 * blockIdx.x, tot);
-}
-
-// Round 6, the fused training step's optimiser launch (cfd_fno_adam_step): the flat Adam above PLUS the work that used to be launches of
-// its own in front of it -- (a) the nMSE normaliser: the head ran with the mse coefficient upstream / n, so every gradient still lacks the
-// factor n / sum (label*mask)^2 = sums[3] / sums[2] (both left by the head's reduction; k_label_energy_part + _coef: two launches, 10 us);
-// (b) the lifting layer's gradient: workgroup c < job.C finishes row c of fc0 from the sum records of k_block<.., STEMG>, stores it (in
-// the same, still unscaled units as every other gradient) and applies Adam to it; the flat part skips those two ranges.
-// DW: decoupled weight decay (adam_update<true>: the `wd` argument is the factor 1 - lr * weight_decay); a variant of its own, so the
-// code of k_adam_f<VEC, false> is what k_adam_f<VEC> was.
-// GUARD (CFD_STEP_SKIP_NONFINITE; the launcher sets it only with clip.buf != NULL): a norm that is not finite -- a NaN or an inf in the
-// gradient, an overflowing sum, an inf or NaN normaliser, a NaN grad_scale -- makes the launch a SKIPPED STEP.  Every workgroup has added
-// up the same records in the same order, so the test is uniform across the grid and each returns before it has loaded an element of
-// p, m or v.  The thread that stores clip[0..1] keeps the two counters at the buffer's end (plain load, add, store: no other thread of the
-// launch and no record of k_gradsq reaches them).  n == 0 is no step at all: the counters stay.  A variant of its own, so the code of
-// k_adam_f<VEC, DW, false> is what k_adam_f<VEC, DW> was.
-template <bool VEC, bool DW = false, bool GUARD = false>
-__global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
-                                                float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip) {
-    __shared__ float s_r[CFD_STEMG_NA][256];
-    __shared__ double s_sq[256];
-    if (sums) gscale *= sums[3] / sums[2];
-    if (clip.buf) {  // (uniform; NULL = the launch of ABI 603: nothing is loaded before the first element)
-        const double sq = clip_total_sq(clip.buf, clip.nrec, s_sq);
-        const double norm = fabs((double)gscale) * sqrt(sq);
-        const double coef = n ? fmin(1.0, (double)clip.max_norm / (norm + 1e-6)) : 1.0;
-        if constexpr (GUARD) {
-            const bool skip = n && !__builtin_isfinite(norm);  // (the build has no fast-math flag: the test is not folded away)
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                clip.buf[0] = (float)norm, clip.buf[1] = skip ? 0.f : (float)coef;
-                if (skip) {
-                    clip.buf[CFD_CLIP_SKIPPED] += 1.f;
-                    clip.buf[CFD_CLIP_CONSECUTIVE] += 1.f;
-                } else if (n) {
-                    clip.buf[CFD_CLIP_CONSECUTIVE] = 0.f;
-                }
-            }
-            if (skip) return;
-        } else {
-            if (blockIdx.x == 0 && threadIdx.x == 0) clip.buf[0] = (float)norm, clip.buf[1] = (float)coef;
-        }
-        gscale *= (float)coef;  // (coef == 1: the same bits as without clipping)
-    }
-    const int njob = job.part ? job.C : 0;
-    const int F = job.in_chan + 3 + job.P;
-    if ((int)blockIdx.x < njob) {
-        const int c = blockIdx.x;
-        stem_combine_channel(job.part, job.nrec, job.spl, job.cp, job.P, job.C, c, s_r);
-        if ((int)threadIdx.x <= F) {
-            const bool bias = (int)threadIdx.x == F;
-            const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
-            const size_t i = bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x;
-            g[i] = gv;
-            adam_update<DW>(p[i], gv, m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-        }
-        return;
-    }
-    const size_t jw0 = (size_t)job.w_off, jw1 = jw0 + (size_t)job.C * F, jb0 = (size_t)job.b_off, jb1 = jb0 + job.C;
-    auto mine = [&](size_t e) { return !(njob && ((e >= jw0 && e < jw1) || (e >= jb0 && e < jb1))); };
-    const size_t t0 = (size_t)(blockIdx.x - njob) * blockDim.x + threadIdx.x, nt = (size_t)(gridDim.x - njob) * blockDim.x;
-    if constexpr (VEC) {
-        const size_t n4 = n >> 2;
-        const size_t jlo = jw0 < jb0 ? jw0 : jb0, jhi = jw1 > jb1 ? jw1 : jb1;
-        for (size_t i = t0; i < n4; i += nt) {
-            if (njob && 4 * i < jhi && 4 * i + 4 > jlo) {  // a unit that touches the lifting layer's ranges: element by element
-                for (size_t e = 4 * i; e < 4 * i + 4; ++e)
-                    if (mine(e)) adam_update<DW>(p[e], g[e], m[e], v[e], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-                continue;
-            }
-            f32x4 pi = reinterpret_cast<const f32x4*>(p)[i], mi = reinterpret_cast<const f32x4*>(m)[i], vi = reinterpret_cast<const f32x4*>(v)[i];
-            const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float pj = pi[j], mj = mi[j], vj = vi[j];
-                adam_update<DW>(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-                pi[j] = pj, mi[j] = mj, vi[j] = vj;
-            }
-            reinterpret_cast<f32x4*>(m)[i] = mi;
-            reinterpret_cast<f32x4*>(v)[i] = vi;
-            reinterpret_cast<f32x4*>(p)[i] = pi;
-        }
-        for (size_t i = 4 * n4 + t0; i < n; i += nt)
-            if (mine(i)) adam_update<DW>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-    } else {
-        for (size_t i = t0; i < n; i += nt)
-            if (mine(i)) adam_update<DW>(p[i], g[i], m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-    }
-}
-
-int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, int decoupled, int guard, void* stream) {
-    CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
-    CFD_REQUIRE(!guard || clip, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_STEP_SKIP_NONFINITE needs grads->clip");
-    CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: step must be >= 1");
-    CFD_REQUIRE(!clip || max_grad_norm > 0.f, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: max_grad_norm must be > 0 (+inf: measure only)");
-    if (n == 0 && !clip) return CFD_OK;
-    StemAdamJob jb = job ? *job : StemAdamJob{};
-    CFD_REQUIRE(!jb.part || (jb.P <= 8 && jb.in_chan + 3 + jb.P < 256), CFD_ERR_UNSUPPORTED, "cfd_fno_adam_step: lifting layer with %d case parameters", jb.P);
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const bool vec = ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0) && n >= 4;
-    size_t blocks = ((vec ? n / 4 : n) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    ClipArgs ca{};
-    if (clip) {  // the norm needs the finished fc0 rows: k_gradsq takes the job, Adam's launch runs the flat update alone
-        const int njob = jb.part ? jb.C : 0;
-        // (with the guard the last two floats are its counters: the records must end in front of them)
-        CFD_REQUIRE(2 + 2 * (njob + CFD_CLIP_MAX_WGS) <= CFD_CLIP_FLOATS - (guard ? 2 : 0), CFD_ERR_UNSUPPORTED,
-                    "cfd_fno_adam_step: clipping with a lifting layer of %d channels", njob);
-        const size_t gsq = n == 0 ? 0 : (blocks < CFD_CLIP_MAX_WGS ? blocks : (size_t)CFD_CLIP_MAX_WGS);
-        ca = ClipArgs{clip, max_grad_norm, (int)gsq + njob};
-        if (ca.nrec > 0) {
-            CFD_PROF_W("k_gradsq", (hipStream_t)stream, 4.0 * n, 2.0 * n);
-            if (vec)
-                hipLaunchKernelGGL(k_gradsq<true>, dim3((unsigned)ca.nrec), dim3(256), 0, (hipStream_t)stream, grad, n, clip, jb);
-            else
-                hipLaunchKernelGGL(k_gradsq<false>, dim3((unsigned)ca.nrec), dim3(256), 0, (hipStream_t)stream, grad, n, clip, jb);
-            CFD_LAUNCH_CHECK("cfd_fno_adam_step");
-        }
-        jb = StemAdamJob{};
-        if (blocks == 0) blocks = 1;  // (n == 0: one workgroup stores clip[0] = 0, clip[1] = 1)
-    }
-    blocks += jb.part ? jb.C : 0;
-    CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
-    const dim3 grid((unsigned)blocks), wg(256);
-    const float rbc1 = (float)bc1, rbc2 = (float)(1.0 / sqrt(bc2));
-    // AdamW: p *= 1 - lr * wd (the factor in double, rounded once, as torch forms it), then Adam on the undecayed gradient
-    const float wdarg = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : weight_decay;
-#define CFD_ADAM_F_LAUNCH(VEC_, DW_, GUARD_)                                                                                           \
-    hipLaunchKernelGGL((k_adam_f<VEC_, DW_, GUARD_>), grid, wg, 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, \
-                       beta2, eps, wdarg, rbc1, rbc2, grad_scale, sums, jb, ca)
-    if (guard) {  // (the variants that can skip the step: clip != NULL was required above)
-        if (decoupled) {
-            if (vec) CFD_ADAM_F_LAUNCH(true, true, true);
-            else CFD_ADAM_F_LAUNCH(false, true, true);
-        } else if (vec) CFD_ADAM_F_LAUNCH(true, false, true);
-        else CFD_ADAM_F_LAUNCH(false, false, true);
-    } else if (decoupled) {
-        if (vec) CFD_ADAM_F_LAUNCH(true, true, false);
-        else CFD_ADAM_F_LAUNCH(false, true, false);
-    } else if (vec) CFD_ADAM_F_LAUNCH(true, false, false);
-    else CFD_ADAM_F_LAUNCH(false, false, false);
-#undef CFD_ADAM_F_LAUNCH
-    CFD_LAUNCH_CHECK("cfd_fno_adam_step");
-    return CFD_OK;
-}
-
-// Gradient accumulation over micro-batches (CFD_STEP_ACCUMULATE of cfd_fno_adam_step): the optimiser launch's place in a pass that is not
-// the group's last.  It finishes the pass's gradient exactly as k_adam_f does -- the deferred normaliser in the scale, workgroup c < job.C
-// the lifting layer's row c, stored into g in the pass's unscaled units -- and its update rule is acc[i] = s * g[i] (INIT: the previous
-// contents are never loaded) or fmaf(s, g[i], acc[i]).  One thread writes each element, no atomics: two calls give the same bits.  12 bytes
-// per element, 8 with INIT; the flat part is k_adam_f's loop (one f32x4 of each buffer per thread and trip, grid capped like Adam's).
-template <bool VEC, bool INIT>
-__global__ __launch_bounds__(256) void k_grad_accum(float* __restrict__ acc, float* __restrict__ g, size_t n, float gscale,
-                                                    const float* __restrict__ sums, const StemAdamJob job) {
-    __shared__ float s_r[CFD_STEMG_NA][256];
-    if (sums) gscale *= sums[3] / sums[2];
-    auto add = [&](float& a, float gv) { a = INIT ? gscale * gv : fmaf(gscale, gv, a); };
-    const int njob = job.part ? job.C : 0;
-    const int F = job.in_chan + 3 + job.P;
-    if ((int)blockIdx.x < njob) {
-        const int c = blockIdx.x;
-        stem_combine_channel(job.part, job.nrec, job.spl, job.cp, job.P, job.C, c, s_r);
-        if ((int)threadIdx.x <= F) {
-            const bool bias = (int)threadIdx.x == F;
-            const float gv = bias ? s_r[0][0] : s_r[stem_feature_slot(threadIdx.x, job.in_chan)][0];
-            const size_t i = bias ? (size_t)job.b_off + c : (size_t)job.w_off + (size_t)c * F + threadIdx.x;
-            g[i] = gv;
-            add(acc[i], gv);
-        }
-        return;
-    }
-    const size_t jw0 = (size_t)job.w_off, jw1 = jw0 + (size_t)job.C * F, jb0 = (size_t)job.b_off, jb1 = jb0 + job.C;
-    auto mine = [&](size_t e) { return !(njob && ((e >= jw0 && e < jw1) || (e >= jb0 && e < jb1))); };
-    const size_t t0 = (size_t)(blockIdx.x - njob) * blockDim.x + threadIdx.x, nt = (size_t)(gridDim.x - njob) * blockDim.x;
-    if constexpr (VEC) {
-        const size_t n4 = n >> 2;
-        const size_t jlo = jw0 < jb0 ? jw0 : jb0, jhi = jw1 > jb1 ? jw1 : jb1;
-        for (size_t i = t0; i < n4; i += nt) {
-            if (njob && 4 * i < jhi && 4 * i + 4 > jlo) {  // a unit that touches the lifting layer's ranges: element by element
-                for (size_t e = 4 * i; e < 4 * i + 4; ++e)
-                    if (mine(e)) add(acc[e], g[e]);
-                continue;
-            }
-            const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i];
-            f32x4 ai;
-            if constexpr (INIT) ai = f32x4{0.f, 0.f, 0.f, 0.f};
-            else ai = reinterpret_cast<const f32x4*>(acc)[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float aj = ai[j];
-                add(aj, gi[j]);
-                ai[j] = aj;
-            }
-            reinterpret_cast<f32x4*>(acc)[i] = ai;
-        }
-        for (size_t i = 4 * n4 + t0; i < n; i += nt)
-            if (mine(i)) add(acc[i], g[i]);
-    } else {
-        for (size_t i = t0; i < n; i += nt)
-            if (mine(i)) add(acc[i], g[i]);
-    }
-}
-
-int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,
-                         void* stream) {
-    CFD_REQUIRE(acc && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
-    if (n == 0) return CFD_OK;
-    const StemAdamJob jb = job ? *job : StemAdamJob{};
-    CFD_REQUIRE(!jb.part || (jb.P <= 8 && jb.in_chan + 3 + jb.P < 256), CFD_ERR_UNSUPPORTED, "cfd_fno_adam_step: lifting layer with %d case parameters", jb.P);
-    const bool vec = ((((uintptr_t)acc | (uintptr_t)grad) & 15) == 0) && n >= 4;
-    size_t blocks = ((vec ? n / 4 : n) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    blocks += jb.part ? jb.C : 0;
-    CFD_PROF_W("k_grad_accum", (hipStream_t)stream, (init ? 8.0 : 12.0) * n, 2.0 * n);  // read g (and acc); write acc
-    const dim3 grid((unsigned)blocks), wg(256);
-    if (vec && init)
-        hipLaunchKernelGGL((k_grad_accum<true, true>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
-    else if (vec)
-        hipLaunchKernelGGL((k_grad_accum<true, false>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
-    else if (init)
-        hipLaunchKernelGGL((k_grad_accum<false, true>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
-    else
-        hipLaunchKernelGGL((k_grad_accum<false, false>), grid, wg, 0, (hipStream_t)stream, acc, grad, n, grad_scale, sums, jb);
-    CFD_LAUNCH_CHECK("cfd_fno_adam_step");
-    return CFD_OK;
-}
-
-// The same step for MANY parameter tensors in one launch (the autograd training paths of the U-Net / ResNet / DeepONet families keep
-// torch's per-tensor parameters: 136 / 28 / 33 tensors).  torch's fused multi-tensor Adam took 3 x 31 us for the U-Net's 4.4 MB and
-// 40 us for the Auto-DeepONet's 2.3 MB -- 7 % of that model's step.  The (p, g, m, v, n) table travels as the kernel argument;
-// workgroups [blk0, blk0 + nblk) belong to item i.  Learning rate and step count come from device scalars when given (a captured
-// HIP graph replays with the values of the moment), bias corrections are formed in fp32 like torch's capturable path.
-#define CFD_ADAM_MAX 80
-#define CFD_MULTI_MAX_BLOCKS 2048u  // workgroups per tensor of the multi-tensor launches (beyond: several trips per thread)
-struct AdamItem {
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    unsigned n, blk0;
-};
-struct AdamBatch {
-    int n;
-    AdamItem it[CFD_ADAM_MAX];
-};
-
-__global__ __launch_bounds__(256) void k_adam_multi(const AdamBatch b, const float* __restrict__ lr_dev, float lr,
-                                                    const float* __restrict__ step_dev, float step, float b1, float b2, float eps,
-                                                    float wd, float gscale) {
-    // this workgroup's item: the last one whose first workgroup is <= blockIdx.x.  Bisection -- seven dependent scalar loads of the
-    // kernel-argument table at most; the linear walk of rounds 3-4 cost the last items' workgroups up to 79 of them
-    int i = 0, hi = b.n;
-    while (hi - i > 1) {
-        const int mid = (i + hi) >> 1;
-        if (blockIdx.x >= b.it[mid].blk0) i = mid;
-        else hi = mid;
-    }
-    const AdamItem& e = b.it[i];
-    const unsigned nblk = (i + 1 < b.n ? b.it[i + 1].blk0 : gridDim.x) - e.blk0;
-    if (lr_dev) lr = lr_dev[0];
-    if (step_dev) step = step_dev[0];
-    // the bias corrections once per workgroup (wave 0), not once per wave: two powf are ~300 VALU instructions, and with one element per
-    // thread they were most of the kernel's issue time
-    __shared__ float s_bc[2];
-    if (threadIdx.x < 64) {
-        const float c1 = 1.f - powf(b1, step), c2 = 1.f / sqrtf(1.f - powf(b2, step));
-        if (threadIdx.x == 0) s_bc[0] = c1, s_bc[1] = c2;
-    }
-    __syncthreads();
-    const float bc1 = s_bc[0], rsqrt_bc2 = s_bc[1];
-    // (bit 31 of n: the item's four buffers are 16-byte aligned -- a thread owns four consecutive elements per trip, the last n % 4
-    // elements go one by one to the item's first threads)
-    const unsigned n = e.n & 0x7fffffffu, t0 = (blockIdx.x - e.blk0) * blockDim.x + threadIdx.x, nt = nblk * blockDim.x;
-    unsigned first = 0;
-    if (e.n >> 31) {
-        const unsigned n4 = n >> 2;
-        for (unsigned k = t0; k < n4; k += nt) {
-            f32x4 pi = reinterpret_cast<const f32x4*>(e.p)[k], mi = reinterpret_cast<const f32x4*>(e.m)[k], vi = reinterpret_cast<const f32x4*>(e.v)[k];
-            const f32x4 gi = reinterpret_cast<const f32x4*>(e.g)[k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float pj = pi[j], mj = mi[j], vj = vi[j];
-                adam_update(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-                pi[j] = pj, mi[j] = mj, vi[j] = vj;
-            }
-            reinterpret_cast<f32x4*>(e.m)[k] = mi;
-            reinterpret_cast<f32x4*>(e.v)[k] = vi;
-            reinterpret_cast<f32x4*>(e.p)[k] = pi;
-        }
-        first = 4 * n4;
-    }
-    for (unsigned k = first + t0; k < n; k += nt) adam_update(e.p[k], e.g[k], e.m[k], e.v[k], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
-}
-
-extern "C" int cfd_adam_multi(int n, float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
-                              const size_t* numel, const float* lr_dev, float lr, const float* step_dev, float step, float beta1,
-                              float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
-    CFD_REQUIRE(n >= 0, CFD_ERR_INVALID_ARG, "cfd_adam_multi: negative count");
-    if (n == 0) return CFD_OK;
-    CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq && numel, CFD_ERR_INVALID_ARG, "cfd_adam_multi: NULL table");
-    CFD_REQUIRE(step_dev || step >= 1.f, CFD_ERR_INVALID_ARG, "cfd_adam_multi: step must be >= 1");
-    for (int base = 0; base < n; base += CFD_ADAM_MAX) {
-        AdamBatch b{};
-        b.n = n - base < CFD_ADAM_MAX ? n - base : CFD_ADAM_MAX;
-        unsigned blocks = 0;
-        double total = 0.0;
-        for (int i = 0; i < b.n; ++i) {
-            const int k = base + i;
-            CFD_REQUIRE(param[k] && grad[k] && exp_avg[k] && exp_avg_sq[k], CFD_ERR_INVALID_ARG, "cfd_adam_multi: NULL pointer in item %d", k);
-            CFD_REQUIRE(numel[k] < (1ull << 31), CFD_ERR_UNSUPPORTED, "cfd_adam_multi: item %d has 2^31 or more elements", k);
-            AdamItem& e = b.it[i];
-            e.p = param[k], e.g = grad[k], e.m = exp_avg[k], e.v = exp_avg_sq[k], e.n = (unsigned)numel[k], e.blk0 = blocks;
-            // ONE trip per thread up to 2048 workgroups per tensor, four elements in 16-byte units where the buffers allow: a thread that
-            // walks several trips pays one memory latency per trip (the Auto-DeepONet's 430 k-element first-layer weight: 7 trips on 256
-            // workgroups), and one element per thread takes more workgroups than the chip holds at once (2300 for that model: two
-            // rounds of the whole latency chain -- table lookup, step / rate scalars, bias corrections, loads)
-            const bool vec = e.n >= 4 && ((((uintptr_t)e.p | (uintptr_t)e.g | (uintptr_t)e.m | (uintptr_t)e.v) & 15) == 0);
-            unsigned nb = ((vec ? e.n / 4 : e.n) + 255) / 256;
-            if (vec) e.n |= 0x80000000u;
-            if (nb < 1) nb = 1;
-            if (nb > CFD_MULTI_MAX_BLOCKS) nb = CFD_MULTI_MAX_BLOCKS;
-            blocks += nb;
-            total += (double)(e.n & 0x7fffffffu);
-        }
-        CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * total, 12.0 * total);
-        hipLaunchKernelGGL(k_adam_multi, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b, lr_dev, lr, step_dev, step, beta1, beta2,
-                           eps, weight_decay, grad_scale);
-        CFD_LAUNCH_CHECK("cfd_adam_multi");
-    }
-    return CFD_OK;
-}
-
-// dst[k][i] = scale * src[k][i] for n tensors in one launch per 80 (the data-parallel path of the graph-replayed models packs every
-// parameter gradient, pre-scaled by 1 / world, into ONE flat buffer behind the captured backward pass: graph.GraphedTrainStep;
-// torch.cat + mul_ + ~136 copy_ launches per U-Net step before).  Same table walk as k_adam_multi.
-struct CopyItem {
-    const float* s;
-    float* d;
-    unsigned n, blk0;
-};
-struct CopyBatch {
-    int n;
-    CopyItem it[CFD_ADAM_MAX];
-};
-__global__ __launch_bounds__(256) void k_scale_copy_multi(const CopyBatch b, float scale) {
-    int i = 0, hi = b.n;  // (bisection, as k_adam_multi)
-    while (hi - i > 1) {
-        const int mid = (i + hi) >> 1;
-        if (blockIdx.x >= b.it[mid].blk0) i = mid;
-        else hi = mid;
-    }
-    const CopyItem& e = b.it[i];
-    const unsigned nblk = (i + 1 < b.n ? b.it[i + 1].blk0 : gridDim.x) - e.blk0;
-    for (unsigned k = (blockIdx.x - e.blk0) * blockDim.x + threadIdx.x; k < e.n; k += nblk * blockDim.x) e.d[k] = e.s[k] * scale;
-}
-
-extern "C" int cfd_scale_copy_multi(int n, const float* const* src, float* const* dst, const size_t* numel, float scale, void* stream) {
-    CFD_REQUIRE(n >= 0, CFD_ERR_INVALID_ARG, "cfd_scale_copy_multi: negative count");
-    if (n == 0) return CFD_OK;
-    CFD_REQUIRE(src && dst && numel, CFD_ERR_INVALID_ARG, "cfd_scale_copy_multi: NULL table");
-    for (int base = 0; base < n; base += CFD_ADAM_MAX) {
-        CopyBatch b{};
-        b.n = n - base < CFD_ADAM_MAX ? n - base : CFD_ADAM_MAX;
-        unsigned blocks = 0;
-        double total = 0.0;
-        for (int i = 0; i < b.n; ++i) {
-            const int k = base + i;
-            CFD_REQUIRE(src[k] && dst[k], CFD_ERR_INVALID_ARG, "cfd_scale_copy_multi: NULL pointer in item %d", k);
-            CFD_REQUIRE(numel[k] < (1ull << 31), CFD_ERR_UNSUPPORTED, "cfd_scale_copy_multi: item %d has 2^31 or more elements", k);
-            CopyItem& e = b.it[i];
-            e.s = src[k], e.d = dst[k], e.n = (unsigned)numel[k], e.blk0 = blocks;
-            unsigned nb = (e.n + 255) / 256;  // (as cfd_adam_multi: one element per thread up to CFD_MULTI_MAX_BLOCKS workgroups per tensor)
-            if (nb < 1) nb = 1;
-            if (nb > CFD_MULTI_MAX_BLOCKS) nb = CFD_MULTI_MAX_BLOCKS;
-            blocks += nb;
-            total += (double)e.n;
-        }
-        CFD_PROF_W("k_scale_copy_multi", (hipStream_t)stream, 8.0 * total, total);
-        hipLaunchKernelGGL(k_scale_copy_multi, dim3(blocks), dim3(256), 0, (hipStream_t)stream, b, scale);
-        CFD_LAUNCH_CHECK("cfd_scale_copy_multi");
-    }
-    return CFD_OK;
-}
-
-extern "C" int cfd_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
-                             float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
-                             void* stream) {
-    CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_adam_flat: NULL pointer");
-    CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_adam_flat: step must be >= 1");
-    if (n == 0) return CFD_OK;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const bool vec = ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0) && n >= 4;
-    size_t blocks = ((vec ? n / 4 : n) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
-    if (vec)
-        hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale);
-    else
-        hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, lr,
-                           beta1, beta2, eps, weight_decay, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale);
-    CFD_LAUNCH_CHECK("cfd_adam_flat");
     return CFD_OK;
 }

@@ -24,11 +24,17 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _lib
-from ._capi import CFD_CLIP_CONSECUTIVE, CFD_CLIP_FLOATS, CFD_CLIP_SKIPPED, CFD_STEP_DECOUPLED_WD, CFD_STEP_SKIP_NONFINITE
+from ._capi import (CFD_CLIP_CONSECUTIVE, CFD_CLIP_FLOATS, CFD_CLIP_SKIPPED, CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE, CFD_STEP_DECOUPLED_WD,
+                    CFD_STEP_SKIP_NONFINITE)
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
 _ACT_DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
+
+
+def _check_tensors(*tensors: Optional[Tensor]) -> None:
+    if any(t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()) for t in tensors):
+        raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
 
 
 def flatten_layout(params: Sequence[Tensor], align: int = 4, trainable: Optional[Sequence[bool]] = None) -> Tuple[List[int], int]:
@@ -489,9 +495,7 @@ class FnoTrainEngine:
     def _begin(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor], flags: int):
         """What every pass starts with: the tensor check, the per-shape state, and the arguments its C calls share --
         (plan, shape, params, grads), (inputs, case_params, mask, label, preds), sums, coef, workspace, stream."""
-        for t in (inputs, label, case_params, mask):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
+        _check_tensors(inputs, label, case_params, mask)
         self._prepare(inputs, case_params)
         self._last = (inputs, case_params, mask, flags)  # optimizer_step finishes what the flags deferred
         model = (self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct))
@@ -532,6 +536,19 @@ class FnoTrainEngine:
             handles.append(self.sync.reduce_slice_async(self.flat.grad, s0, s1))
         return self.sync.wait_all(handles)
 
+    def _adam_step(self, params, grads, dst: Tensor, grad: Tensor, stepping: bool, scale: float, flags: int, inputs: Tensor,
+                   case_params: Tensor, mask: Optional[Tensor], sums: Optional[Tensor] = None, ws: Optional[Tensor] = None) -> None:
+        """The cfd_fno_adam_step call of every route: ``params`` / ``grads`` structs, ``dst`` the flat buffer it writes (parameters or
+        accumulator), ``grad`` the one it reads; ``stepping``: with moments, hyper-parameters, step count and the optimiser's own flags (an
+        accumulate call takes none: NULL and zeros); then the pass's data tensors, and its loss sums and workspace where they are not the engine's own."""
+        state = ((self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, *self.betas, self.eps, self.weight_decay,
+                  self.step_count) if stepping else (None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 0))
+        flags |= (self._dw_flag | self._skip_flag) if stepping else 0
+        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(params), ctypes.byref(grads), inputs.data_ptr(),
+                      case_params.data_ptr(), None if mask is None else mask.data_ptr(), (self.sums if sums is None else sums).data_ptr(),
+                      (self.ws if ws is None else ws).data_ptr(), dst.data_ptr(), grad.data_ptr(), *state, scale, self.loss_id,
+                      self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
+
     def _no_open_group(self, what: str) -> None:
         if self._accum_open:
             raise RuntimeError(f"FnoTrainEngine.{what}: an accumulation group is open (accumulate() without its apply_accumulated()); "
@@ -545,16 +562,12 @@ class FnoTrainEngine:
         step (cfd_fno_adam_step with CFD_STEP_ACCUMULATE: it finishes what the pass deferred, then adds instead of stepping).  ``first``
         starts a group -- the accumulator is overwritten, never read; ``weight`` is usually 1 / (micro-batches of the group).  Returns the
         device tensor of ``train_step`` for THIS micro-batch.  ``apply_accumulated()`` closes the group."""
-        from ._capi import CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE
         if not first and not self._accum_open:
             raise RuntimeError("FnoTrainEngine.accumulate: first=False without an open group (the accumulator holds nothing to add to)")
         self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
         self._ensure_accum()
         flags = self.defer_flags | CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if first else 0)
-        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.astruct), ctypes.byref(self.gstruct),
-                      inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
-                      self.ws.data_ptr(), self.accum.data_ptr(), self.flat.grad.data_ptr(), None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0,
-                      0.0, 0, float(weight), self.loss_id, self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
+        self._adam_step(self.astruct, self.gstruct, self.accum, self.flat.grad, False, float(weight), flags, inputs, case_params, mask)
         self._last = (inputs, case_params, mask, 0)  # (the deferred work of this pass is done)
         self._accum_open = True
         return self.sums
@@ -610,7 +623,6 @@ class FnoTrainEngine:
         rides in the loss coefficients (``upstream``).  fp32 activation storage only.
         ``detach=True`` (the pushforward trick): the fed-back frame is a constant, so the window is K plain micro-batches of weight
         ``weight / K`` -- ``accumulate`` itself, with deferred launches, one-pass head and bf16 storage as there."""
-        from ._capi import CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE
         K = len(labels_seq)
         if K < 1:
             raise ValueError("FnoTrainEngine.accumulate_window: no label frames")
@@ -640,9 +652,7 @@ class FnoTrainEngine:
             self._win_last = w["preds"]
             return w["sums"]
         a, st = self.api, torch.cuda.current_stream().cuda_stream
-        for t in (inputs, case_params, mask, *labels_seq):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError("FnoTrainEngine expects contiguous float32 CUDA tensors")
+        _check_tensors(inputs, case_params, mask, *labels_seq)
         self._ensure_accum()
         plan, sh, pr = self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct)
         cp, mk = case_params.data_ptr(), None if mask is None else mask.data_ptr()
@@ -668,8 +678,8 @@ class FnoTrainEngine:
             for phase in range(1 if one_pass[k] else 0, (self.L + 1 if k >= 1 else self.last_phase) + 1):
                 a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *data, gext, coef, sums, ws, phase, self.loss_id, 0, 0, st)
             flags = CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if (first and k == K - 1) else 0)
-            a.call("cfd_fno_adam_step", plan, sh, ctypes.byref(self.astruct), gr, data[0], cp, mk, sums, ws, self.accum.data_ptr(),
-                   self.flat.grad.data_ptr(), None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 0, float(weight), self.loss_id, 0, flags, st)
+            self._adam_step(self.astruct, w["gs"][k], self.accum, self.flat.grad, False, float(weight), flags, xs[k], case_params, mask,
+                            w["sums"][k], w["ws"][k])  # (act_dtype is 0 here: bf16 storage was refused above)
         self._last = (inputs, case_params, mask, 0)
         self._accum_open = True
         self._win_last = w["preds"]
@@ -691,18 +701,10 @@ class FnoTrainEngine:
             raise RuntimeError("FnoTrainEngine.apply_accumulated: nothing accumulated (call accumulate(..., first=True) first)")
         scale = self.sync.all_reduce(self.accum)
         self.step_count += 1
-        inputs, case_params, mask, _ = self._last
-        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.astruct),
-                      inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
-                      self.ws.data_ptr(), self.flat.data.data_ptr(), self.accum.data_ptr(), self.exp_avg.data_ptr(),
-                      self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                      self.step_count, scale, self.loss_id, self.act_dtype, self._step_flags(0), torch.cuda.current_stream().cuda_stream)
+        self._adam_step(self.pstruct, self.astruct, self.flat.data, self.accum, True, scale, 0, *self._last[:3])
         self._accum_open = False
         self._grad_pending_scale = False
         self._grad_in_accum = True
-
-    def _step_flags(self, flags: int) -> int:
-        return flags | self._dw_flag | self._skip_flag
 
     def optimizer_step(self, grad_scale: float = 1.0):
         self._no_open_group("optimizer_step")
@@ -717,12 +719,7 @@ class FnoTrainEngine:
             raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping, skip_nonfinite and AdamW need the pass that produced the "
                                "gradients (forward_backward / train_step) first")
         if flags or self.clip is not None or adamw:
-            self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(self.pstruct), ctypes.byref(self.gstruct),
-                          inputs.data_ptr(), case_params.data_ptr(), None if mask is None else mask.data_ptr(), self.sums.data_ptr(),
-                          self.ws.data_ptr(), self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
-                          self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                          self.step_count, grad_scale, self.loss_id, self.act_dtype, self._step_flags(flags),
-                          torch.cuda.current_stream().cuda_stream)
+            self._adam_step(self.pstruct, self.gstruct, self.flat.data, self.flat.grad, True, grad_scale, flags, inputs, case_params, mask)
             self._last = (inputs, case_params, mask, 0)  # (a second optimizer_step on the same gradients must not redo the deferred work)
             self._grad_pending_scale = bool(flags & 1) and self.loss_id == _LOSS_IDS["nmse"] and self._route_defers
             return

@@ -1,5 +1,5 @@
 """Checks of gradient accumulation over micro-batches in the fused FNO step (CFD_STEP_ACCUMULATE / CFD_STEP_ACCUM_INIT of cfd_fno_adam_step's
-`flags`; k_grad_accum in cfdbench_amd/csrc/pointwise.hip).  Used by tests/test_emul_fno_accum.py (CPU, SIMT emulator) and
+`flags`; k_grad_accum in cfdbench_amd/csrc/optim.hip).  Used by tests/test_emul_fno_accum.py (CPU, SIMT emulator) and
 tests/test_gpu_fno_accum.py (MI355X).  Everything runs through the C ABI on tests/backends.py's hostile memory.
 
 The rule (include/cfdbench_amd.h): with CFD_STEP_ACCUMULATE the call finishes the pass's gradient as the optimiser call does and then
@@ -7,9 +7,9 @@ The rule (include/cfdbench_amd.h): with CFD_STEP_ACCUMULATE the call finishes th
 with s = grad_scale, times sums[3] / sums[2] where the nMSE normaliser is deferred, formed in fp32.  The optimiser step on the accumulated
 gradient is the call without the two bits, flags = 0, with the accumulator as its gradient buffer.
 
-Shapes: tests/clip_checks.py's CASES (each the smallest that reaches its path) plus one whose lifting-layer ranges do not end on a multiple
-of four floats -- hidden 5 with 4 case parameters: fc0.weight is [0, 45), fc0.bias [48, 53) of the flat buffer, so the units of four at
-44 and at 52 are half the job's and half the flat loop's.
+Shapes: tests/clip_checks.py's CASES (each the smallest that reaches its path), among them "odd_ranges", whose lifting-layer ranges do not
+end on a multiple of four floats -- hidden 5 with 4 case parameters: fc0.weight is [0, 45), fc0.bias [48, 53) of the flat buffer, so the
+units of four at 44 and at 52 are half the job's and half the flat loop's.
 
 Bounds: one fp32 rounding per element is a relative error of at most 2^-24, i.e. at most 3.6e-15 of relative nMSE (1e-13 asked); a sum of
 three such terms rounds three times (1e-12 asked).  Gradients against the fp64 oracle at the bounds the fused step's own tests hold them to:
@@ -38,8 +38,8 @@ SUM_TOL = 1e-12    # acc against the fp64 sum of three terms
 GRAD_TOL, GRAD_TOL_PAD = 1e-11, 1e-9
 N_MICRO, N_STEPS = 3, 3
 
-CASES = dict(CC.CASES)
-CASES["odd_ranges"] = dict(B=1, C=5, L=1, H=64, W=64, which="nmse", flags=7, job=True, P=4)  # fc0 ranges end inside a unit of four
+# (odd_ranges' misaligned twin is clipping's: here check_misaligned_gives_the_aligned_bits places whole cases off the boundary)
+CASES = {k: v for k, v in CC.CASES.items() if k != "odd_ranges_misaligned"}
 _DATA, _RUNS = {}, {}
 
 same_bits, _bits = CC.same_bits, CC._bits

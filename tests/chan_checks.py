@@ -214,8 +214,12 @@ def check_fno_train_step(be, B, C, L, H, W, cin, cout, p=5, which="nmse", flags=
     the first gradient of the flagged run (every tensor) against the oracle."""
     params = make_params(pseed, C, L, 12, 12, p, cin, cout, 4.0)
     batch = make_batch(bseed, B, H, W, p, cin, cout, border)
-    # (out_chan > 2 defers nothing: the buffer holds the loss's own gradient whatever the flags say)
+    # (out_chan > 2 defers nothing: the buffer holds the loss's own gradient whatever the flags say; at out_chan <= 2 the deferred
+    # normaliser leaves the gradient of sum d^2 / n, rescaled here as K.check_fno_train_step_deferred does)
     out, layout = F.run_fused_steps(be, params, batch, L, C, H, W, p, which=which, flags=flags, steps=steps)
+    for fl, o in out.items():
+        if cout <= 2 and (fl & 1) and which == "nmse":
+            o["g1"] = o["g1"] * (o["sums1"][3] / o["sums1"][2])
     a, b = out[0], out[flags]
     res = {"params": nm(b["flat"], a["flat"]), "preds": nm(b["preds1"], a["preds1"]), "grad_vs_immediate": nm(b["g1"], a["g1"]),
            "sums": float(np.max(np.abs(b["sums1"] - a["sums1"]) / np.abs(a["sums1"])))}

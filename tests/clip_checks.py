@@ -1,5 +1,5 @@
 """Checks of gradient-norm clipping inside the fused FNO step's optimiser call (cfd_fno_params.clip / max_grad_norm of the grads struct, ABI
-604; k_gradsq and the clip prologue of k_adam_f in cfdbench_amd/csrc/pointwise.hip).  Used by tests/test_emul_fno_clip.py (CPU, SIMT
+604; k_gradsq and the clip prologue of k_adam_f in cfdbench_amd/csrc/optim.hip).  Used by tests/test_emul_fno_clip.py (CPU, SIMT
 emulator), tests/test_gpu_fno_clip.py (MI355X) and tests/test_cpu_clip.py (the restatement against torch).
 
 The rule, restated in NumPy fp64 (clip_rule; torch.nn.utils.clip_grad_norm_ with norm_type 2):
@@ -28,7 +28,7 @@ CLIP_TOL = 2.5e-7   # clip[0], clip[1] against fp64: one fp32 rounding (2^-24) o
 ADAM_TOL = 1e-9     # moments and parameter deltas against oracle.adam_step (tests/test_emul_kernels.py holds cfd_adam_flat to it)
 LR = 1e-3
 
-# name -> B, C, L, H, W, which, flags, grad_scale, (m1, m2, pad); each the smallest that reaches its path
+# name -> B, C, L, H, W, which, flags, grad_scale, (m1, m2, pad, P = 5 case parameters); each the smallest that reaches its path
 CASES = {
     "job_and_deferred_scale": dict(B=2, C=20, L=2, H=64, W=64, which="nmse", flags=7, job=True),   # lifting-layer job in k_gradsq, sums[3]/sums[2] in s
     "job_mae": dict(B=1, C=8, L=1, H=64, W=64, which="mae", flags=7, job=True),                    # the job without the scale deferral
@@ -37,6 +37,10 @@ CASES = {
     "wide": dict(B=1, C=40, L=1, H=64, W=64, which="mse", flags=7),                       # the wide route defers nothing
     "padded": dict(B=1, C=6, L=1, H=8, W=8, which="nmse", flags=7, m1=2, m2=2, pad=2),    # tests/pad_checks.py's smallest padded shape
     "misaligned": dict(B=2, C=20, L=2, H=64, W=64, which="nmse", flags=7, job=True, misalign=True),  # scalar forms of both kernels
+    # hidden 5 with 4 case parameters: fc0.weight is [0, 45), fc0.bias [48, 53) of the flat buffer, so the units of four at 44 and at 52 are
+    # half the job's and half the flat walk's (the edge rule of the walk every optimiser kernel shares)
+    "odd_ranges": dict(B=1, C=5, L=1, H=64, W=64, which="nmse", flags=7, job=True, P=4),
+    "odd_ranges_misaligned": dict(B=1, C=5, L=1, H=64, W=64, which="nmse", flags=7, job=True, P=4, misalign=True),
 }
 _DATA, _RUNS = {}, {}
 
@@ -68,12 +72,12 @@ def case_data(name):
     c = CASES[name]
     key = tuple((k, v) for k, v in sorted(c.items()) if k not in ("misalign", "job"))
     if key not in _DATA:
-        m1, m2 = c.get("m1", 12), c.get("m2", 12)
+        m1, m2, p = c.get("m1", 12), c.get("m2", 12), c.get("P", 5)
         if c.get("pad", 0):
-            _DATA[key] = (CK.make_params(3, c["C"], c["L"], m1, m2, 5), CK.make_batch(4, c["B"], c["H"], c["W"], 5, border=True))
+            _DATA[key] = (CK.make_params(3, c["C"], c["L"], m1, m2, p), CK.make_batch(4, c["B"], c["H"], c["W"], p, border=True))
         else:
-            _DATA[key] = (synth.make_fno_params(27, c["C"], c["L"], m1, m2, 5, spectral_gain=4.0),
-                          synth.make_batch(28, c["B"], c["H"], c["W"], 5, border_mask=True))
+            _DATA[key] = (synth.make_fno_params(27, c["C"], c["L"], m1, m2, p, spectral_gain=4.0),
+                          synth.make_batch(28, c["B"], c["H"], c["W"], p, border_mask=True))
     return _DATA[key]
 
 
@@ -96,7 +100,7 @@ def run_steps(be, name, max_norm, steps=3, again=0):
     c = CASES[name]
     api, P = be.api, be.ptr
     B, C, L, H, W = c["B"], c["C"], c["L"], c["H"], c["W"]
-    m1, m2, pad, p = c.get("m1", 12), c.get("m2", 12), c.get("pad", 0), 5
+    m1, m2, pad, p = c.get("m1", 12), c.get("m2", 12), c.get("pad", 0), c.get("P", 5)
     wid, flags, gs_ = WHICH[c["which"]], c["flags"], float(c.get("grad_scale", 1.0))
     params, batch = case_data(name)
     layout, numel, flat0 = F.flat_layout(params, L)

@@ -1,5 +1,5 @@
 """Checks of fine-tuning on the fused FNO step: decoupled weight decay inside the optimiser launch (CFD_STEP_DECOUPLED_WD of cfd_fno_adam_step's
-`flags`; k_adam_f<VEC, true> in cfdbench_amd/csrc/pointwise.hip) and whole steps over a TRAINABLE SUBSET at the C ABI -- compact flat buffers,
+`flags`; k_adam_f<VEC, true> in cfdbench_amd/csrc/optim.hip) and whole steps over a TRAINABLE SUBSET at the C ABI -- compact flat buffers,
 frozen tensors in storage of their own, their gradients in a sink, a backward pass that stops behind the shallowest trainable tensor
 (cfdbench_amd/engine.py: flatten_layout, last_backward_phase, mask_defer_flags).  Used by tests/test_cpu_finetune.py (the rule against
 torch.optim.AdamW), tests/test_emul_finetune.py (CPU, SIMT emulator) and tests/test_gpu_finetune.py (MI355X).

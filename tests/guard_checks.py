@@ -1,5 +1,5 @@
 """Checks of skipping non-finite steps inside the fused FNO step's optimiser call (CFD_STEP_SKIP_NONFINITE of cfd_fno_adam_step's `flags`;
-k_adam_f<VEC, DW, true> in cfdbench_amd/csrc/pointwise.hip).  Used by tests/test_emul_fno_guard.py (CPU, SIMT emulator) and
+k_adam_f<VEC, DW, true> in cfdbench_amd/csrc/optim.hip).  Used by tests/test_emul_fno_guard.py (CPU, SIMT emulator) and
 tests/test_gpu_fno_guard.py (MI355X).  Everything runs through the C ABI on tests/backends.py's hostile memory.
 
 The rule (include/cfdbench_amd.h): with the bit, norm = |s| * sqrt(sum_i grad[i]^2) in fp64 -- the quantity clipping defines, s = grad_scale

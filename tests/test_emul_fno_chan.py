@@ -102,6 +102,16 @@ def test_fused_train_step_chan(be):
     _assert_all(res, 1e-9)
 
 
+def test_fused_train_step_on_odd_fc0_ranges(be):
+    """The deferred step (two output channels: flags = 7 defers) at hidden 5 with 4 case parameters: fc0.weight is [0, 45), fc0.bias
+    [48, 53) of the flat buffer, so k_adam_f's walk meets 16-byte units that are half the lifting-layer job's (accum_checks' "odd_ranges").
+    The bounds of test_emul_kernels.py::test_fused_train_step_with_deferred_launches, on every tensor."""
+    res = CK.check_fno_train_step(be, 1, 5, 1, 64, 64, 2, 2, p=4, flags=7)
+    print(res)
+    assert res.pop("sums") < 1e-6 and res.pop("preds") == 0.0
+    _assert_all(res, 1e-11)
+
+
 def test_refusals_chan(be):
     """out_chan = 9 and bf16 storage with out_chan = 3 raise CfdError; outputs still poisoned (guard bands: the autouse fixture)."""
     res = CK.check_refusals(be)

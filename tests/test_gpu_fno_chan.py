@@ -111,6 +111,14 @@ def test_fused_train_step_chan(be, H, W):
     _assert_all(res, 1e-9)
 
 
+def test_fused_train_step_on_odd_fc0_ranges(be):
+    """tests/test_emul_fno_chan.py's row: k_adam_f's walk over 16-byte units that are half the lifting-layer job's."""
+    res = CK.check_fno_train_step(be, 1, 5, 1, 64, 64, 2, 2, p=4, flags=7)
+    print(res)
+    assert res.pop("sums") < 1e-6 and res.pop("preds") == 0.0
+    _assert_all(res, 1e-11)
+
+
 def test_refusals_chan(be):
     res = CK.check_refusals(be, H=64, W=64)
     assert all(res.values()), res

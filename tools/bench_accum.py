@@ -15,7 +15,6 @@ B = 256 per micro-batch, 64 x 64, width 20, L = 4, one GPU).  Writes profiles/ac
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import statistics
 import subprocess
@@ -106,10 +105,7 @@ def kernel_alone(torch, eng, data, init):
     flags = eng.defer_flags | CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if init else 0)
 
     def call():
-        eng.api.call("cfd_fno_adam_step", eng.plan, ctypes.byref(eng.shape), ctypes.byref(eng.astruct), ctypes.byref(eng.gstruct),
-                     inputs.data_ptr(), cp.data_ptr(), mask.data_ptr(), eng.sums.data_ptr(), eng.ws.data_ptr(), eng.accum.data_ptr(),
-                     eng.flat.grad.data_ptr(), None, None, eng.flat.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0.5, eng.loss_id, eng.act_dtype, flags,
-                     torch.cuda.current_stream().cuda_stream)
+        eng._adam_step(eng.astruct, eng.gstruct, eng.accum, eng.flat.grad, False, 0.5, flags, inputs, cp, mask)
     us = timed_window(torch, call, 20, 0.05) * 1e6
     eng.apply_accumulated()
     return round(us, 3)
