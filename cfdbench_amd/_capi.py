@@ -181,6 +181,9 @@ _SIGS = {
                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfd_fno_adam_step": (_I, [_P, C.POINTER(FnoShape), C.POINTER(FnoParams), C.POINTER(FnoParams), _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _I, _F, _I, _I, _I, _P]),
+    # the same 25 arguments, then `float* ema, float ema_decay` (ema = NULL: cfd_fno_adam_step itself)
+    "cfd_fno_adam_step_ema": (_I, [_P, C.POINTER(FnoShape), C.POINTER(FnoParams), C.POINTER(FnoParams), _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _I, _F, _I, _I, _I, _P, _P, _F]),
     "cfd_fno_backward": (_I, [_P, C.POINTER(FnoShape), C.POINTER(FnoParams), C.POINTER(FnoParams),
                               _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cfd_fno_backward_phase": (_I, [_P, C.POINTER(FnoShape), C.POINTER(FnoParams), C.POINTER(FnoParams),

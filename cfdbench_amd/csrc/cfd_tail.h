@@ -247,9 +247,11 @@ int cfd_int_stemg_combine(const cfd_plan* p, const float* part, const float* cp,
 // decoupled != 0 (CFD_STEP_DECOUPLED_WD): AdamW -- param *= 1 - lr * weight_decay, then Adam on the undecayed gradient (k_adam_f<VEC, true>).
 // guard != 0 (CFD_STEP_SKIP_NONFINITE; needs clip): a norm that is not finite skips the step -- k_adam_f<VEC, DW, true> returns before it
 // touches param or the moments, clip[1] = 0, and clip[CFD_CLIP_SKIPPED] / clip[CFD_CLIP_CONSECUTIVE] count.
+// ema != NULL (cfd_fno_adam_step_ema): n floats laid out like param; ema[i] = fmaf(ema_decay, ema[i], (1 - ema_decay) * param_new[i]) in
+// the same launch (k_adam_f<VEC, DW, GUARD, true>); 0 <= ema_decay < 1, which the entry point in fno.cpp has checked.
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, int decoupled, int guard, void* stream);
+                        float max_grad_norm, int decoupled, int guard, float* ema, float ema_decay, void* stream);
 // CFD_STEP_ACCUMULATE of cfd_fno_adam_step: the same deferred work (`sums`, `job`), but acc[i] = s * grad[i] (init) or fmaf(s, grad[i], acc[i])
 // instead of Adam (the same stem_row and flat_walk, AccumOp for AdamOp); `acc` is laid out like `grad` (k_grad_accum)
 int cfd_int_grad_accum_f(float* acc, float* grad, size_t n, float grad_scale, const float* sums, const StemAdamJob* job, int init,

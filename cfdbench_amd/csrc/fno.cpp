@@ -451,11 +451,22 @@ extern "C" int cfd_fno_backward(const cfd_plan* p, const cfd_fno_shape* s, const
 
 // The optimiser launch of the fused training step: Adam over the flat buffers, the deferred nMSE normaliser (sums[3] / sums[2] on top of
 // grad_scale) and the lifting layer's gradient rows (see include/cfdbench_amd.h).  `params` / `grads` point into `param` / `grad`.
+// cfd_fno_adam_step_ema: the same call with an exponential moving average of the parameters kept inside the optimiser launch
+// (ema == NULL: cfd_fno_adam_step itself, which forwards here).
 extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, const cfd_fno_params* prm, const cfd_fno_params* g,
                                  const float* inputs, const float* case_params, const float* mask, const float* sums, void* ws,
                                  float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                                  float beta2, float eps, float weight_decay, int step, float grad_scale, int which, int act_dtype,
                                  int flags, void* stream) {
+    return cfd_fno_adam_step_ema(p, s, prm, g, inputs, case_params, mask, sums, ws, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
+                                 weight_decay, step, grad_scale, which, act_dtype, flags, stream, nullptr, 0.f);
+}
+
+extern "C" int cfd_fno_adam_step_ema(const cfd_plan* p, const cfd_fno_shape* s, const cfd_fno_params* prm, const cfd_fno_params* g,
+                                     const float* inputs, const float* case_params, const float* mask, const float* sums, void* ws,
+                                     float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, int step, float grad_scale, int which, int act_dtype,
+                                     int flags, void* stream, float* ema, float ema_decay) {
     CFD_TRY(check_shape("cfd_fno_adam_step", p, s, act_dtype));
     CFD_REQUIRE(prm && g && ws && param && grad, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(act_dtype == CFD_DT_F32 || act_dtype == CFD_DT_BF16, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: act_dtype %d", act_dtype);
@@ -471,6 +482,11 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
     // CFD_STEP_SKIP_NONFINITE: the optimiser call skips a step whose gradient norm is not finite.  The norm is the clip buffer's, so the
     // bit needs it; with CFD_STEP_ACCUMULATE no norm is taken and the bit is ignored (the guard fires later, on the accumulator)
     const bool guard = !accumulate && (flags & CFD_STEP_SKIP_NONFINITE) != 0;
+    // the average follows the parameters: an accumulate call writes none, so it ignores both arguments.  (The test is written so that a
+    // NaN decay fails it.)
+    if (accumulate) ema = nullptr;
+    CFD_REQUIRE(!ema || (ema_decay >= 0.f && ema_decay < 1.f), CFD_ERR_INVALID_ARG,
+                "cfd_fno_adam_step_ema: ema_decay must be >= 0 and < 1 (got %g)", (double)ema_decay);
     CFD_REQUIRE(!guard || g->clip, CFD_ERR_INVALID_ARG,
                 "cfd_fno_adam_step: CFD_STEP_SKIP_NONFINITE needs grads->clip (max_grad_norm = +inf: guard without clipping)");
     const View v(p, s, 1, act_dtype, ws);
@@ -498,5 +514,5 @@ extern "C" int cfd_fno_adam_step(const cfd_plan* p, const cfd_fno_shape* s, cons
                                     (flags & CFD_STEP_ACCUM_INIT) != 0, stream);
     return cfd_int_adam_flat_f(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                rt.scale ? sums : nullptr, rt.stem ? &job : nullptr, g->clip, g->max_grad_norm,
-                               (flags & CFD_STEP_DECOUPLED_WD) != 0, guard, stream);
+                               (flags & CFD_STEP_DECOUPLED_WD) != 0, guard, ema, ema_decay, stream);
 }

@@ -96,27 +96,50 @@ __device__ __forceinline__ void flat_walk(const float* __restrict__ g, size_t n,
     }
 }
 
-template <bool DW>
+// EMA (cfd_fno_adam_step_ema): an exponential moving average of the parameters, updated while the new parameter is still in a register --
+// ema[i] = fmaf(d, ema[i], (1 - d) * p_new), the ema.mul_(d).add_(p, alpha = 1 - d) of timm and diffusers.  The product is made opaque so
+// that it is rounded on its own: d = 0 then gives ema[i] == p_new bit for bit for any finite ema[i] (but for the sign of a zero: 0 * e + -0 is +0).  8 more bytes per element, no launch.
+template <bool EMA>
+struct EmaPart {};
+template <>
+struct EmaPart<true> {
+    float* __restrict__ ema;
+    float decay;
+};
+template <bool EMA>
+__device__ __forceinline__ float ema_update(const EmaPart<EMA>& a, float e, float p) {
+    return fmaf(a.decay, e, cfd_opaque_f((1.f - a.decay) * p));
+}
+
+template <bool DW, bool EMA = false>
 struct AdamOp {
     float* __restrict__ p;
     const float* __restrict__ g;
     float *__restrict__ m, *__restrict__ v;
     float lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale;
+    EmaPart<EMA> a;  // (empty without EMA)
     template <typename I>  // (I: size_t on the flat buffer, unsigned in k_adam_multi)
-    __device__ __forceinline__ void one(I i, float gv) const { adam_update<DW>(p[i], gv, m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale); }
+    __device__ __forceinline__ void one(I i, float gv) const {
+        adam_update<DW>(p[i], gv, m[i], v[i], lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
+        if constexpr (EMA) a.ema[i] = ema_update(a, a.ema[i], p[i]);
+    }
     template <typename I>
     __device__ __forceinline__ void four(I i) const {
         f32x4 pi = reinterpret_cast<const f32x4*>(p)[i], mi = reinterpret_cast<const f32x4*>(m)[i], vi = reinterpret_cast<const f32x4*>(v)[i];
         const f32x4 gi = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 ei;
+        if constexpr (EMA) ei = reinterpret_cast<const f32x4*>(a.ema)[i];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float pj = pi[j], mj = mi[j], vj = vi[j];
             adam_update<DW>(pj, gi[j], mj, vj, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale);
             pi[j] = pj, mi[j] = mj, vi[j] = vj;
+            if constexpr (EMA) ei[j] = ema_update(a, ei[j], pj);
         }
         reinterpret_cast<f32x4*>(m)[i] = mi;
         reinterpret_cast<f32x4*>(v)[i] = vi;
         reinterpret_cast<f32x4*>(p)[i] = pi;
+        if constexpr (EMA) reinterpret_cast<f32x4*>(a.ema)[i] = ei;
     }
 };
 // acc[i] = s * g[i] (INIT: the previous contents are never loaded) or fmaf(s, g[i], acc[i])
@@ -238,10 +261,13 @@ __global__ __launch_bounds__(256) void k_gradsq(float* __restrict__ g, size_t n,
 // up the same records in the same order, so the test is uniform across the grid and each returns before it has loaded an element of
 // p, m or v.  The thread that stores clip[0..1] keeps the two counters at the buffer's end (plain load, add, store: no other thread of the
 // launch and no record of k_gradsq reaches them).  n == 0 is no step at all: the counters stay.
-template <bool VEC, bool DW = false, bool GUARD = false>
+// EMA (cfd_fno_adam_step_ema with ema != NULL): AdamOp<DW, true> on both paths, the flat walk and the job's rows; a skipped step has
+// returned before any element is loaded, so the average keeps its bits with the parameters.  Without EMA `ea` is an empty struct.
+template <bool VEC, bool DW = false, bool GUARD = false, bool EMA = false>
 __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                 size_t n, float lr, float b1, float b2, float eps, float wd, float bc1, float rsqrt_bc2,
-                                                float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip) {
+                                                float gscale, const float* __restrict__ sums, const StemAdamJob job, const ClipArgs clip,
+                                                const EmaPart<EMA> ea) {
     __shared__ float s_r[CFD_STEMG_NA][256];
     __shared__ double s_sq[256];
     if (sums) gscale *= sums[3] / sums[2];
@@ -267,7 +293,7 @@ __global__ __launch_bounds__(256) void k_adam_f(float* __restrict__ p, float* __
         gscale *= (float)coef;  // (coef == 1: the same bits as without clipping)
     }
     const JobRanges r(job);
-    const AdamOp<DW> op{p, g, m, v, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale};
+    const AdamOp<DW, EMA> op{p, g, m, v, lr, b1, b2, eps, wd, bc1, rsqrt_bc2, gscale, ea};
     if ((int)blockIdx.x < r.njob) stem_row(g, job, r, s_r, op);
     else flat_walk<VEC>(g, n, r, blockDim.x, op);
 }
@@ -316,7 +342,7 @@ static void with_bools(F&& f, bool b, Rest... rest) {
 
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,
-                        float max_grad_norm, int decoupled, int guard, void* stream) {
+                        float max_grad_norm, int decoupled, int guard, float* ema, float ema_decay, void* stream) {
     CFD_REQUIRE(param && grad && exp_avg && exp_avg_sq, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: NULL pointer");
     CFD_REQUIRE(!guard || clip, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: CFD_STEP_SKIP_NONFINITE needs grads->clip");
     CFD_REQUIRE(step >= 1, CFD_ERR_INVALID_ARG, "cfd_fno_adam_step: step must be >= 1");
@@ -325,7 +351,10 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
     StemAdamJob jb;
     CFD_TRY(checked_job(job, jb));
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const FlatGrid fg = flat_grid(n, {param, grad, exp_avg, exp_avg_sq});
+    // k_gradsq does not touch the average: its form and its records are those of the call without `ema` (fg0), so the clip buffer is that
+    // call's bit for bit wherever the average lies; Adam's launch takes the average's pointer into its alignment test (fg)
+    const FlatGrid fg0 = flat_grid(n, {param, grad, exp_avg, exp_avg_sq});
+    const FlatGrid fg = ema ? flat_grid(n, {param, grad, exp_avg, exp_avg_sq, ema}) : fg0;
     unsigned blocks = fg.blocks;
     ClipArgs ca{};
     if (clip) {  // the norm needs the finished fc0 rows: k_gradsq takes the job, Adam's launch runs the flat update alone
@@ -333,28 +362,30 @@ int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_av
         // (with the guard the last two floats are its counters: the records must end in front of them)
         CFD_REQUIRE(2 + 2 * (njob + CFD_CLIP_MAX_WGS) <= CFD_CLIP_FLOATS - (guard ? 2 : 0), CFD_ERR_UNSUPPORTED,
                     "cfd_fno_adam_step: clipping with a lifting layer of %d channels", njob);
-        const unsigned gsq = blocks < CFD_CLIP_MAX_WGS ? blocks : (unsigned)CFD_CLIP_MAX_WGS;  // (n == 0: none)
+        const unsigned gsq = fg0.blocks < CFD_CLIP_MAX_WGS ? fg0.blocks : (unsigned)CFD_CLIP_MAX_WGS;  // (n == 0: none)
         ca = ClipArgs{clip, max_grad_norm, (int)gsq + njob};
         if (ca.nrec > 0) {
             CFD_PROF_W("k_gradsq", (hipStream_t)stream, 4.0 * n, 2.0 * n);
             with_bools([&](auto V) {
                 hipLaunchKernelGGL(k_gradsq<CFD_B(V)>, dim3((unsigned)ca.nrec), dim3(256), 0, (hipStream_t)stream, grad, n, clip, jb);
-            }, fg.vec);
+            }, fg0.vec);
             CFD_LAUNCH_CHECK("cfd_fno_adam_step");
         }
         jb = StemAdamJob{};
         if (blocks == 0) blocks = 1;  // (n == 0: one workgroup stores clip[0] = 0, clip[1] = 1)
     }
     blocks += jb.part ? jb.C : 0;
-    CFD_PROF_W("k_adam", (hipStream_t)stream, 28.0 * n, 12.0 * n);  // read p, g, m, v; write p, m, v
+    CFD_PROF_W("k_adam", (hipStream_t)stream, (ema ? 36.0 : 28.0) * n, (ema ? 14.0 : 12.0) * n);  // read p, g, m, v; write p, m, v; the average both ways
     const float rbc1 = (float)bc1, rbc2 = (float)(1.0 / sqrt(bc2));
     // AdamW: p *= 1 - lr * wd (the factor in double, rounded once, as torch forms it), then Adam on the undecayed gradient
     const float wdarg = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : weight_decay;
     // (guard: the variants that can skip the step: clip != NULL was required above)
-    with_bools([&](auto V, auto D, auto G) {
-        hipLaunchKernelGGL((k_adam_f<CFD_B(V), CFD_B(D), CFD_B(G)>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                           exp_avg_sq, n, lr, beta1, beta2, eps, wdarg, rbc1, rbc2, grad_scale, sums, jb, ca);
-    }, fg.vec, decoupled != 0, guard != 0);
+    with_bools([&](auto V, auto D, auto G, auto E) {
+        EmaPart<CFD_B(E)> ea{};
+        if constexpr (CFD_B(E)) ea = EmaPart<true>{ema, ema_decay};
+        hipLaunchKernelGGL((k_adam_f<CFD_B(V), CFD_B(D), CFD_B(G), CFD_B(E)>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad,
+                           exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, wdarg, rbc1, rbc2, grad_scale, sums, jb, ca, ea);
+    }, fg.vec, decoupled != 0, guard != 0, ema != nullptr);
     CFD_LAUNCH_CHECK("cfd_fno_adam_step");
     return CFD_OK;
 }

@@ -12,10 +12,15 @@ decoupled weight decay inside the same optimiser launch (CFD_STEP_DECOUPLED_WD).
 
 Unattended runs: ``skip_nonfinite=True`` skips an optimiser step whose gradient norm is not finite inside that same launch
 (CFD_STEP_SKIP_NONFINITE): weights and moments keep their bits, the counts stay on the device.
+
+Averaged weights: ``ema_decay=d`` keeps an exponential moving average of the trainable weights, updated inside that same launch
+(cfd_fno_adam_step_ema): no launch more, a skipped step leaves it alone.  ``averaged()`` swaps it into the model for evaluation.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -346,7 +351,8 @@ class FnoTrainEngine:
     def __init__(self, model, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
                  overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None,
-                 trainable: Optional[Sequence[str]] = None, optimizer: str = "adam", skip_nonfinite: bool = False):
+                 trainable: Optional[Sequence[str]] = None, optimizer: str = "adam", skip_nonfinite: bool = False,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         """``trainable``: state_dict key prefixes (``{"fc1", "fc2"}``, ``{"blocks.3", "fc1", "fc2"}``) of the parameters to train; the
         others are frozen (their ``requires_grad`` is set to match).  None: the engine honours ``requires_grad`` as it finds it.  The
         flat buffers (parameters, gradient, moments, accumulator, what a data-parallel run exchanges) hold the trainable tensors only, and
@@ -375,6 +381,18 @@ class FnoTrainEngine:
         ``step_count`` advances on a skipped step too: the bias corrections after a skip are those of t, not of the number of applied
         steps (the one difference from a ``torch.amp.GradScaler`` skip; it keeps the guarded step without skips bitwise the unguarded
         one).
+
+        ``ema_decay`` = d, 0 <= d < 1 (None: no average, the calls of an engine without the argument): ``self.ema``, a flat buffer laid out
+        like ``flat.data`` -- compact, the trainable tensors only; a frozen tensor's average is the tensor itself -- starts as a copy of
+        the initial weights and follows every applied optimiser step inside its launch (cfd_fno_adam_step_ema, which is then the optimiser
+        call on every route, as with clipping and AdamW): ``ema = fmaf(d_t, ema, (1 - d_t) * new weight)``, timm's and diffusers'
+        ``ema.mul_(d).add_(p, alpha=1 - d)``.  No launch more.  d_t (``ema_decay_at``) is d, or with ``ema_warmup`` min(d, (1 + t) / (10 + t))
+        with t = ``step_count`` of the step (1 for the first; it runs on over a skipped step, like the bias corrections), formed on the
+        host in double and rounded once, to the fp32 the call takes.  It holds on ``train_step`` / ``optimizer_step`` /
+        ``train_step_graph`` (the call is outside the replay), ``apply_accumulated`` (groups and rollout windows: ``accumulate`` calls never
+        touch the average), frozen subsets, AdamW and clipping; a step skipped by ``skip_nonfinite`` leaves the average's bits; data-
+        parallel, every rank applies the same bits, so the replicas' averages stay identical with no collective.  ``ema_state_dict()``
+        and ``averaged()`` read it; ``state_dict()`` carries it.
 
         ``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
         activations a_0 .. a_L are rounded to bf16 when stored -- half the bytes of what the backward pass re-reads -- and the
@@ -455,6 +473,14 @@ class FnoTrainEngine:
         self.astruct = None
         self._accum_open = False   # between an accumulate() and its apply_accumulated()
         self._grad_in_accum = False  # whether the last optimiser step read the accumulator (gradients())
+        # the averaged weights (cfd_fno_adam_step_ema): laid out like flat.data, a copy of the initial weights
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        if self.ema_decay is not None and not 0.0 <= self.ema_decay < 1.0:  # (NaN fails the comparison too)
+            raise ValueError("ema_decay must be >= 0 and < 1 (None: no averaged weights)")
+        self.ema_warmup = bool(ema_warmup)
+        self.ema: Optional[Tensor] = None if self.ema_decay is None else self.flat.data.detach().clone()
+        self._ema_scratch: Optional[Tensor] = None  # averaged(): where the trained weights wait
+        self._averaged = False
 
     # ------------------------------------------------------------------------------------------------
     def _prepare(self, inputs: Tensor, case_params: Tensor):
@@ -544,12 +570,22 @@ class FnoTrainEngine:
         state = ((self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat.numel, self.lr, *self.betas, self.eps, self.weight_decay,
                   self.step_count) if stepping else (None, None, self.flat.numel, 0.0, 0.0, 0.0, 0.0, 0.0, 0))
         flags |= (self._dw_flag | self._skip_flag) if stepping else 0
-        self.api.call("cfd_fno_adam_step", self.plan, ctypes.byref(self.shape), ctypes.byref(params), ctypes.byref(grads), inputs.data_ptr(),
+        # with averaged weights the entry that carries them, on every route; an accumulate call writes no parameter and takes the plain one
+        entry, tail = "cfd_fno_adam_step", ()
+        if stepping and self.ema is not None:
+            entry, tail = "cfd_fno_adam_step_ema", (self.ema.data_ptr(), self.ema_decay_at(self.step_count))
+        self.api.call(entry, self.plan, ctypes.byref(self.shape), ctypes.byref(params), ctypes.byref(grads), inputs.data_ptr(),
                       case_params.data_ptr(), None if mask is None else mask.data_ptr(), (self.sums if sums is None else sums).data_ptr(),
                       (self.ws if ws is None else ws).data_ptr(), dst.data_ptr(), grad.data_ptr(), *state, scale, self.loss_id,
-                      self.act_dtype, flags, torch.cuda.current_stream().cuda_stream)
+                      self.act_dtype, flags, torch.cuda.current_stream().cuda_stream, *tail)
+
+    def _not_averaged(self, what: str) -> None:
+        if self._averaged:
+            raise RuntimeError(f"FnoTrainEngine.{what}: inside averaged() the model holds the averaged weights; training on them would "
+                               "lose the trained ones -- leave the context first")
 
     def _no_open_group(self, what: str) -> None:
+        self._not_averaged(what)
         if self._accum_open:
             raise RuntimeError(f"FnoTrainEngine.{what}: an accumulation group is open (accumulate() without its apply_accumulated()); "
                                "the step would run on the last micro-batch's gradient alone")
@@ -562,6 +598,7 @@ class FnoTrainEngine:
         step (cfd_fno_adam_step with CFD_STEP_ACCUMULATE: it finishes what the pass deferred, then adds instead of stepping).  ``first``
         starts a group -- the accumulator is overwritten, never read; ``weight`` is usually 1 / (micro-batches of the group).  Returns the
         device tensor of ``train_step`` for THIS micro-batch.  ``apply_accumulated()`` closes the group."""
+        self._not_averaged("accumulate")
         if not first and not self._accum_open:
             raise RuntimeError("FnoTrainEngine.accumulate: first=False without an open group (the accumulator holds nothing to add to)")
         self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
@@ -623,6 +660,7 @@ class FnoTrainEngine:
         rides in the loss coefficients (``upstream``).  fp32 activation storage only.
         ``detach=True`` (the pushforward trick): the fed-back frame is a constant, so the window is K plain micro-batches of weight
         ``weight / K`` -- ``accumulate`` itself, with deferred launches, one-pass head and bf16 storage as there."""
+        self._not_averaged("accumulate_window")
         K = len(labels_seq)
         if K < 1:
             raise ValueError("FnoTrainEngine.accumulate_window: no label frames")
@@ -715,10 +753,11 @@ class FnoTrainEngine:
         # norm is taken inside cfd_fno_adam_step, which with flags = 0 is cfd_adam_flat otherwise
         adamw = self._dw_flag != 0  # (decoupled decay exists in cfd_fno_adam_step alone: the optimiser call on every route)
         # (skip_nonfinite holds a clip buffer: the guard exists in cfd_fno_adam_step alone, like clipping)
-        if (self.clip is not None or adamw) and inputs is None:
-            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping, skip_nonfinite and AdamW need the pass that produced the "
-                               "gradients (forward_backward / train_step) first")
-        if flags or self.clip is not None or adamw:
+        ema = self.ema is not None  # (the averaged weights exist in cfd_fno_adam_step_ema alone)
+        if (self.clip is not None or adamw or ema) and inputs is None:
+            raise RuntimeError("FnoTrainEngine.optimizer_step: gradient clipping, skip_nonfinite, AdamW and ema_decay need the pass that "
+                               "produced the gradients (forward_backward / train_step) first")
+        if flags or self.clip is not None or adamw or ema:
             self._adam_step(self.pstruct, self.gstruct, self.flat.data, self.flat.grad, True, grad_scale, flags, inputs, case_params, mask)
             self._last = (inputs, case_params, mask, 0)  # (a second optimizer_step on the same gradients must not redo the deferred work)
             self._grad_pending_scale = bool(flags & 1) and self.loss_id == _LOSS_IDS["nmse"] and self._route_defers
@@ -771,6 +810,47 @@ class FnoTrainEngine:
         self._need_guard("last_step_skipped")
         return self.clip[1] == 0
 
+    # ---- averaged weights --------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if self.ema is None:
+            raise RuntimeError(f"FnoTrainEngine.{what}: the engine was built without ema_decay")
+
+    def ema_decay_at(self, t: int) -> float:
+        """The decay of optimiser step t (``step_count`` of that step, 1 for the first) as a double: ``ema_decay``, with ``ema_warmup``
+        min(ema_decay, (1 + t) / (10 + t)).  The call rounds it once, to fp32."""
+        self._need_ema("ema_decay_at")
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+
+    def ema_state_dict(self) -> Dict[str, Tensor]:
+        """The model's ``state_dict`` (reference key names, complex64 spectral weights) with the averaged weights: trainable tensors from
+        the average, frozen ones (and buffers) from the model.  Copies: later steps do not change them."""
+        self._need_ema("ema_state_dict")
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for k, p_, off, t in zip(self.param_names, self.flat.params, self.flat.offsets, self.flat.trainable):
+            if t:
+                sl = self.ema[off:off + p_.numel() * (2 if p_.is_complex() else 1)]
+                sd[k] = (torch.view_as_complex(sl.view(*p_.shape, 2)) if p_.is_complex() else sl.view(p_.shape)).clone()
+        return sd
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Context manager: inside it the model's storage holds the averaged weights (validation, a test run, a rollout), on exit the
+        trained ones are back, bit for bit.  Two device copies each way through one scratch buffer; no pointer moves, so captured graphs
+        and ``FnoRollout`` objects stay valid.  Frozen tensors are their own average.  Raises while an accumulation group is open; an
+        training call inside the context raises too."""
+        self._need_ema("averaged")
+        self._no_open_group("averaged")  # (also: not inside averaged() already)
+        if self._ema_scratch is None:
+            self._ema_scratch = torch.empty_like(self.flat.data)
+        self._ema_scratch.copy_(self.flat.data)
+        self.flat.data.copy_(self.ema)
+        self._averaged = True
+        try:
+            yield self.model
+        finally:
+            self.flat.data.copy_(self._ema_scratch)
+            self._averaged = False
+
     def train_step(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None) -> Tensor:
         """One optimisation step; returns the device tensor [sum sq err, sum abs err, sum sq label, n] of THIS rank's
         batch (no host sync -- read it with .tolist() only when logging)."""
@@ -788,11 +868,16 @@ class FnoTrainEngine:
     def state_dict(self) -> Dict[str, object]:
         """Adam moments (flat, in ``abi_parameters`` order), step count and learning rate.  The weights themselves live in
         the model's ``state_dict`` (the flat buffer is what the model's parameters view).  With ``skip_nonfinite`` also
-        ``skipped_steps`` as an int (fetched here: saving synchronises anyway); an engine without the guard writes the state it always did."""
+        ``skipped_steps`` as an int (fetched here: saving synchronises anyway); an engine without the guard writes the state it always did.
+        With ``ema_decay`` also ``ema`` (the flat average) and ``ema_decay``; an engine without it writes neither."""
         state = dict(exp_avg=self.exp_avg.detach().clone(), exp_avg_sq=self.exp_avg_sq.detach().clone(),
                      step_count=int(self.step_count), lr=float(self.lr), numel=int(self.flat.numel), trainable=list(self.trainable_names))
         if self.skip_nonfinite:
             state["skipped_steps"] = int(self.clip[CFD_CLIP_SKIPPED].item())
+        if self.ema is not None:
+            if self._averaged:
+                raise RuntimeError("FnoTrainEngine.state_dict: inside averaged() the model holds the averaged weights")
+            state["ema"], state["ema_decay"] = self.ema.detach().clone(), float(self.ema_decay)
         return state
 
     def load_state_dict(self, state: Dict[str, object]) -> None:
@@ -809,6 +894,10 @@ class FnoTrainEngine:
         if self.skip_nonfinite:  # (a state without the key -- an unguarded run's -- means 0; the run of consecutive skips starts anew)
             self.clip[CFD_CLIP_SKIPPED] = float(state.get("skipped_steps", 0))
             self.clip[CFD_CLIP_CONSECUTIVE] = 0.0
+        if self.ema is not None:
+            # a state without the key -- a run without the average -- restarts it from the weights the model holds now: load the model's
+            # weights first.  The decay stays this engine's (a resumed run may change it).
+            self.ema.copy_(state["ema"].to(self.device) if state.get("ema") is not None else self.flat.data)
 
     def scores(self) -> Dict[str, float]:
         """{mse, rmse, mae, nmse} of the last step (loss.py:27-35).  Synchronises."""

@@ -37,7 +37,14 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     torch.nn.utils.clip_grad_norm_ is tested on the host, ONE HOST SYNC PER OPTIMISER STEP; the log line and train_state.pt carry the
     skipped count; not with --graph 1; a run resumed with the other value just continues, the count from the state),
     ``max_consecutive_skips`` (with --skip_nonfinite 1: abort with a RuntimeError once that many optimiser steps in a row were skipped --
-    checked at the log interval on the fused path, per step on the eager ones; the last good checkpoint stays; 0 = never abort).
+    checked at the log interval on the fused path, per step on the eager ones; the last good checkpoint stays; 0 = never abort),
+    ``ema_decay`` (D in (0, 1): an exponential moving average of the trainable weights, ``ema = D ema + (1 - D) weights`` behind every
+    applied optimiser step -- --fused 1: inside the engine's optimiser launch (FnoTrainEngine(ema_decay=D)), eager paths:
+    ``common.EagerEma``; every checkpoint epoch also writes ``ckpt-{ep}/model_ema.pt`` beside ``model.pt``, train_state.pt carries the
+    average; 0.0 = off; not with --graph 1),
+    ``ema_warmup`` (1: the decay of optimiser step t is min(D, (1 + t) / (10 + t))),
+    ``ema_eval`` (1: validation and the final test run on the averaged weights; the trained ones are back afterwards; the multi-step
+    rollout of the averaged weights is ``python -m cfdbench_amd.harness.multistep_ema``, which takes test_multistep's flags).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -69,7 +76,7 @@ _FLAGS: Dict[str, Any] = dict(
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
     fused_accumulation_steps=1, unroll_detach=0, freeze="", train_only="", optimizer="adam", init_from="",
-    skip_nonfinite=0, max_consecutive_skips=100,
+    skip_nonfinite=0, max_consecutive_skips=100, ema_decay=0.0, ema_warmup=0, ema_eval=0,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
@@ -153,6 +160,12 @@ def is_args_valid(args: Args) -> None:
     assert args.max_consecutive_skips >= 0, "--max_consecutive_skips counts skipped optimiser steps in a row (0 = never abort)"
     if args.graph:
         assert not args.skip_nonfinite, "--graph 1 with --skip_nonfinite 1 is not built: cfd_adam_multi has no flags to carry the guard"
+    assert 0.0 <= args.ema_decay < 1.0, "--ema_decay is the decay of the averaged weights, 0 <= D < 1 (0 = no average)"
+    assert args.ema_warmup in (0, 1) and args.ema_eval in (0, 1), "--ema_warmup / --ema_eval are 0 or 1"
+    if not args.ema_decay > 0.0:
+        assert not args.ema_warmup and not args.ema_eval, "--ema_warmup / --ema_eval are options of --ema_decay D > 0"
+    if args.graph:
+        assert not args.ema_decay > 0.0, "--graph 1 with --ema_decay is not built: cfd_adam_multi has no averaged form"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

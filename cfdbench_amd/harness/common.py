@@ -2,6 +2,7 @@
 schemas are what scripts/visualization/get_result.py:19-37 and plot_multistep_inference.py:107-110 read."""
 from __future__ import annotations
 
+import contextlib
 import json
 from pathlib import Path
 from typing import List, Optional, Union
@@ -134,13 +135,90 @@ class SkipGuard:
         return norm, False
 
 
-def load_best_ckpt(model, output_dir: Path) -> Path:  # common.py:278-284
+class EagerEma:
+    """--ema_decay on the eager training paths: an exponential moving average of the TRAINABLE parameters with the rule of the fused
+    engine (FnoTrainEngine(ema_decay=): cfd_fno_adam_step_ema) in torch -- ``ema.mul_(d_t).add_(p, alpha=1 - d_t)`` with d_t =
+    ``decay``, or with ``warmup`` min(decay, (1 + t) / (10 + t)), t = the optimiser step's number (1 for the first; it runs on over a
+    skipped step).  d_t and 1 - d_t are the fp32 values the engine's kernel works with: d_t formed in double and rounded once, 1 - d_t
+    formed in fp32.  The average starts as a copy of the weights; frozen parameters (and buffers) are their own average.  ``update`` is
+    called behind every optimiser step with whether it was applied (``SkipGuard.eager_step``): a skipped step leaves the average alone."""
+
+    def __init__(self, model, decay: float, warmup: bool = False):
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError("ema_decay must be >= 0 and < 1")
+        self.model, self.decay, self.warmup = model, float(decay), bool(warmup)
+        self.step_count = 0
+        self.named = [(k, p_) for k, p_ in model.named_parameters() if p_.requires_grad]
+        self.shadow = [p_.detach().clone() for _, p_ in self.named]
+
+    def decay_at(self, t: int) -> float:
+        return min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+
+    @torch.no_grad()
+    def update(self, applied: bool = True) -> None:
+        self.step_count += 1
+        if not applied:
+            return
+        d = torch.tensor(self.decay_at(self.step_count), dtype=torch.float32)
+        d, omd = float(d), float(torch.tensor(1.0, dtype=torch.float32) - d)
+        for e, (_, p_) in zip(self.shadow, self.named):
+            e.mul_(d).add_(p_.detach(), alpha=omd)
+
+    def ema_state_dict(self):
+        """The model's ``state_dict`` (reference keys) with the averaged tensors in place of the trainable ones; copies."""
+        sd = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        for (k, _), e in zip(self.named, self.shadow):
+            sd[k] = e.detach().clone()
+        return sd
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside: the model holds the averaged weights; on exit the trained ones are back, bit for bit."""
+        with torch.no_grad():
+            saved = [p_.detach().clone() for _, p_ in self.named]
+            for (_, p_), e in zip(self.named, self.shadow):
+                p_.copy_(e)
+        try:
+            yield self.model
+        finally:
+            with torch.no_grad():
+                for (_, p_), s in zip(self.named, saved):
+                    p_.copy_(s)
+
+    def state_dict(self):
+        return dict(ema=[e.detach().clone() for e in self.shadow], ema_step_count=int(self.step_count), ema_decay=self.decay)
+
+    def load_state_dict(self, state) -> None:
+        """A state without the average (a run without --ema_decay) restarts it from the weights the model holds now."""
+        with torch.no_grad():
+            src = state.get("ema") if state else None
+            for i, (e, (_, p_)) in enumerate(zip(self.shadow, self.named)):
+                e.copy_(p_.detach() if src is None else src[i].to(e.device))
+        self.step_count = int(state.get("ema_step_count", 0)) if state else 0
+
+
+def averaged_weights(ema):
+    """``with averaged_weights(x):`` -- x an FnoTrainEngine with ema_decay, an EagerEma, or None (no average: nothing happens)."""
+    return contextlib.nullcontext() if ema is None else ema.averaged()
+
+
+def best_ckpt_file(output_dir: Path, use_ema: bool = False) -> Path:
+    """``model.pt`` of the ckpt-* directory with the smallest dev loss -- with ``use_ema`` the averaged weights the run wrote beside it
+    (``model_ema.pt``, --ema_decay); a run that kept none is an error that names the file."""
     print(f"Finding the best checkpoint from {output_dir}")
     best = get_best_ckpt(output_dir)
     assert best is not None, f"no ckpt-*/scores.json under {output_dir}"
-    print(f"Loading best checkpoint from {best}")
-    load_ckpt(model, best / "model.pt")
-    return best
+    if use_ema and not (best / "model_ema.pt").exists():
+        raise FileNotFoundError(f"{best / 'model_ema.pt'} does not exist: the run that wrote {best.name} kept no averaged weights (train "
+                                "it with --ema_decay D), so there is nothing to load")
+    return best / ("model_ema.pt" if use_ema else "model.pt")
+
+
+def load_best_ckpt(model, output_dir: Path, use_ema: bool = False) -> Path:  # common.py:278-284
+    path = best_ckpt_file(output_dir, use_ema)
+    print(f"Loading best checkpoint from {path.parent}")
+    load_ckpt(model, path)
+    return path.parent
 
 
 # ---- plotting (common.py:35-158): same artefact names; out of scope for acceleration, skipped without matplotlib ----

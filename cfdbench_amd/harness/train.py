@@ -28,7 +28,7 @@ from ..models.deeponet import DeepONet
 from ..models.ffn import FfnModel
 from ..models.loss import loss_name_to_fn
 from .args import Args, is_args_valid
-from .common import (SkipGuard, apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot_loss,
+from .common import (EagerEma, SkipGuard, apply_trainable, averaged_weights, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot_loss,
                      plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
@@ -102,7 +102,8 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
           lr_scheduler_kind: str = "step", lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5,
           early_stopping_patience: int = 0, early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1,
           graph: bool = False, max_grad_norm: float = 0.0, optimizer_kind: str = "adam", weight_decay: float = 0.0,
-          init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100):
+          init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100, ema_decay: float = 0.0,
+          ema_warmup: bool = False, ema_eval: bool = False):
     """src/train.py:148-253: fwd -> ``loss["nmse"].backward()`` -> Adam -> zero_grad; StepLR per epoch.
     ``optimizer_kind`` / ``weight_decay`` / ``init_from`` and the model's ``requires_grad`` flags (--freeze / --train_only): as
     harness/train_auto.py:train.
@@ -113,7 +114,9 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
     ``torch.nn.utils.clip_grad_norm_`` before every optimiser step (after the gradient exchange; not with ``graph``); the log line
     then carries ``grad_norm``.  ``skip_nonfinite`` / ``max_consecutive_skips``: an optimiser step whose gradient norm is not finite is
     skipped, ``common.SkipGuard.eager_step`` (one host sync per optimiser step; not with ``graph``); its micro-batches' losses stay out of
-    the loss history, the log line and train_state.pt carry ``skipped``."""
+    the loss history, the log line and train_state.pt carry ``skipped``.  ``ema_decay`` / ``ema_warmup`` / ``ema_eval``: averaged weights
+    (``common.EagerEma``, updated behind every applied optimiser step; ``model_ema.pt`` beside ``model.pt``, the average in
+    train_state.pt, validation on the averaged weights with ``ema_eval``; not with ``graph``): as harness/train_auto.py:train."""
     rank, world = _rank_world()
     output_dir = Path(output_dir)
     clip = float(max_grad_norm) > 0.0
@@ -124,6 +127,13 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
     if skip_nonfinite and graph:
         raise NotImplementedError("--skip_nonfinite needs --graph 0: cfd_adam_multi has no flags to carry the guard")
     guard = SkipGuard(skip_nonfinite, max_consecutive_skips)
+    use_ema = float(ema_decay) > 0.0
+    if not 0.0 <= float(ema_decay) < 1.0:  # (NaN fails the comparison too)
+        raise ValueError("ema_decay must be >= 0 and < 1 (0 = no averaged weights)")
+    if use_ema and graph:
+        raise NotImplementedError("--ema_decay needs --graph 0: cfd_adam_multi has no averaged form")
+    if (ema_warmup or ema_eval) and not use_ema:
+        raise ValueError("--ema_warmup / --ema_eval are options of --ema_decay D > 0")
     if world > 1:
         broadcast_model_state(model)
 
@@ -156,6 +166,7 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
                              fused=not any(p_.is_complex() for p_ in model.parameters()))  # (torch's fused form takes real parameters only)
     else:
         optimizer = make_optimizer(model.parameters(), optimizer_kind, lr, weight_decay)
+    ema = EagerEma(model, float(ema_decay), bool(ema_warmup)) if use_ema else None  # (behind init_from: it starts from those weights)
     graphed = None
     schedule = LrSchedule(lr_scheduler_kind, lr, num_epochs, optimizer, lr_step_size=lr_step_size, lr_gamma=lr_gamma,
                           factor=lr_scheduler_factor, patience=lr_scheduler_patience)
@@ -171,6 +182,8 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
         check_resume_state(state, fused=False, world=world)
         model.load_state_dict(torch.load(output_dir / state["ckpt"] / "model.pt", map_location="cpu"))
         optimizer.load_state_dict(state["optimizer"])
+        if use_ema:  # (a state without the average restarts it from the checkpoint's weights, loaded above)
+            ema.load_state_dict(state.get("eager_ema") or {})
         if graph:  # the rate of a capturable Adam is a device tensor
             for g_ in optimizer.param_groups:
                 g_["lr"] = torch.tensor(float(g_["lr"]), device="cuda")
@@ -225,6 +238,8 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
                     if clip:
                         grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
                     optimizer.step()
+                if use_ema:
+                    ema.update(applied)
                 optimizer.zero_grad()
             if applied:
                 ep_train_losses.append(loss.item())  # src/train.py:203
@@ -252,13 +267,16 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
         if (ep + 1) % eval_interval == 0 and rank == 0:
             ckpt_dir = output_dir / f"ckpt-{ep}"
             ckpt_dir.mkdir(exist_ok=True, parents=True)
-            dev_scores = evaluate(model, dev_data, ckpt_dir, plot_interval=plot_interval)["scores"]
+            with averaged_weights(ema if ema_eval else None):  # (--ema_eval 1: validation on the averaged weights)
+                dev_scores = evaluate(model, dev_data, ckpt_dir, plot_interval=plot_interval)["scores"]
             dump_json(dev_scores, ckpt_dir / "dev_loss.json")
             dump_json(ep_train_losses, ckpt_dir / "train_loss.json")
             ckpt_path = ckpt_dir / "model.pt"
             if ckpt_path.exists():
                 copyfile(ckpt_path, ckpt_dir / "backup_model.pt")
             torch.save({k: v.detach().clone() for k, v in model.state_dict().items()}, ckpt_path)
+            if use_ema:  # the averaged weights beside it, same keys
+                torch.save({k: v.cpu() for k, v in ema.ema_state_dict().items()}, ckpt_dir / "model_ema.pt")
             dev_loss = float(np.mean(dev_scores["mean"]["nmse"]))
             dump_json(dict(ep=ep, train_loss=float(np.mean(ep_train_losses)), dev_loss=dev_loss,
                            time=time.time() - ep_start_time), ckpt_dir / "scores.json")
@@ -268,7 +286,8 @@ def train(model: CfdModel, train_data, dev_data, output_dir: Path, num_epochs: i
             torch.save(dict(format=2, ep=ep, global_step=global_step, train_losses=all_train_losses + ep_train_losses,
                             ckpt=ckpt_dir.name, optimizer=optimizer.state_dict(), scheduler=schedule.state_dict(),
                             early_stopping=stopper.state_dict(), rng=torch.get_rng_state(), world=world,
-                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {})), tmp)
+                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {}),
+                            **(dict(eager_ema=ema.state_dict()) if use_ema else {})), tmp)
             tmp.replace(state_path)
         if world > 1:  # every rank follows rank 0's validation-driven decisions (plateau rate, early stop)
             flags = torch.tensor([schedule.lr, float(stop)], dtype=torch.float64, device="cuda" if torch.cuda.is_available() else "cpu")
@@ -364,10 +383,12 @@ def main(argv=None):
               early_stopping_patience=args.early_stopping_patience if args.early_stop else 0,
               early_stopping_delta=args.early_stopping_delta, gradient_accumulation_steps=args.gradient_accumulation_steps,
               graph=bool(args.graph), max_grad_norm=args.max_grad_norm, optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
-              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips)
+              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips,
+              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval))
     if "test" in args.mode and rank == 0:
         args.save(str(output_dir / "test_args.json"))
-        load_best_ckpt(model, output_dir)
+        # (--ema_eval 1: the run chose its best checkpoint by the averaged weights' dev loss; the test runs on those weights)
+        load_best_ckpt(model, output_dir, use_ema=bool(args.ema_eval))
         test(model, data=test_data, output_dir=output_dir / "test", batch_size=1, plot_interval=10)
     if world > 1:
         dist.barrier()

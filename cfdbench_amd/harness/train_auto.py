@@ -34,7 +34,7 @@ from ..models.fno.fno2d import Fno2d
 from ..unroll import collate_windows, unroll_windows, unrolled_loss
 from .args import Args, is_args_valid
 from .autoregressive import init_model
-from .common import (SkipGuard, apply_trainable, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
+from .common import (EagerEma, SkipGuard, apply_trainable, averaged_weights, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
                      plot_predictions)
 from .schedule import EarlyStopping, LrSchedule
 from .dist_util import (average_buffers, broadcast_model_state, check_resume_state, init_distributed, rank_world,
@@ -181,7 +181,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           lr_scheduler_factor: float = 0.5, lr_scheduler_patience: int = 5, early_stopping_patience: int = 0,
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
           unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False, optimizer_kind: str = "adam",
-          weight_decay: float = 0.0, init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100):
+          weight_decay: float = 0.0, init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100,
+          ema_decay: float = 0.0, ema_warmup: bool = False, ema_eval: bool = False):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     Fine-tuning: the model's ``requires_grad`` flags are honoured on every path (``common.apply_trainable``: --freeze / --train_only set
@@ -225,6 +226,15 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     optimiser steps in a row were skipped -- fused: checked at the log interval, where the loop reads device scalars anyway, on every
     rank; eager: at the step.  Nothing is written then: the last good checkpoint stays.  Not with ``graph``.
 
+    ``ema_decay`` = D > 0: an exponential moving average of the trainable weights, ``ema = d_t ema + (1 - d_t) weights`` behind every
+    APPLIED optimiser step (d_t = D, with ``ema_warmup`` min(D, (1 + t) / (10 + t)); the reference ships one for its diffusion trainer,
+    src/train_diffusers.py: EMAModel).  ``fused``: inside the engine's optimiser launch (FnoTrainEngine(ema_decay=)), no launch more, a
+    step skipped on the device leaves it alone; eager paths: ``common.EagerEma``, the same rule in torch, updated only when
+    ``SkipGuard.eager_step`` applied the step.  Every checkpoint epoch also writes ``model_ema.pt`` beside ``model.pt`` (reference keys:
+    ``load_ckpt`` / --init_from / harness/multistep_ema.py read it) and train_state.pt carries the average, so ``resume`` continues it
+    bitwise.  ``ema_eval``: validation runs on the averaged weights (the trained ones are back afterwards), so ``dev_loss``, the plateau
+    schedule, early stopping and the best checkpoint are the averaged model's.  Not with ``graph``: cfd_adam_multi has no such form.
+
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
     other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop.
     ``gradient_accumulation_steps`` = N > 1 with ``fused``: FnoTrainEngine.accumulate per micro-batch (weight 1 / group) and
@@ -240,6 +250,13 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     if skip_nonfinite and graph:
         raise NotImplementedError("--skip_nonfinite needs --graph 0: cfd_adam_multi has no flags to carry the guard")
     guard = SkipGuard(skip_nonfinite, max_consecutive_skips)
+    use_ema = float(ema_decay) > 0.0
+    if not 0.0 <= float(ema_decay) < 1.0:  # (NaN fails the comparison too)
+        raise ValueError("ema_decay must be >= 0 and < 1 (0 = no averaged weights)")
+    if use_ema and graph:
+        raise NotImplementedError("--ema_decay needs --graph 0: cfd_adam_multi has no averaged form")
+    if (ema_warmup or ema_eval) and not use_ema:
+        raise ValueError("--ema_warmup / --ema_eval are options of --ema_decay D > 0")
     unroll = int(unroll_steps)
     detach = bool(unroll_detach)
     if detach and unroll <= 1:
@@ -319,7 +336,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         # (adam: weight_decay stays unused, as in the reference)
         engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None,
                                 optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0,
-                                skip_nonfinite=guard.enabled)
+                                skip_nonfinite=guard.enabled, ema_decay=float(ema_decay) if use_ema else None, ema_warmup=bool(ema_warmup))
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -336,6 +353,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                              fused=not any(p_.is_complex() for p_ in model.parameters()))  # (torch's fused form takes real parameters only)
     else:
         optimizer = make_optimizer(model.parameters(), optimizer_kind, lr, weight_decay)
+    # the averaged weights: the engine's own (inside its optimiser launch), or the same rule in torch behind the eager optimiser step
+    ema = None if not use_ema else engine if engine is not None else EagerEma(model, float(ema_decay), bool(ema_warmup))
     graphed = None
     schedule = LrSchedule(lr_scheduler_kind, lr, num_epochs, optimizer, lr_step_size=lr_step_size, lr_gamma=lr_gamma,
                           factor=lr_scheduler_factor, patience=lr_scheduler_patience)
@@ -356,6 +375,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             engine.load_state_dict(state["optimizer"])
         else:
             optimizer.load_state_dict(state["optimizer"])
+            if use_ema:  # (a state without the average restarts it from the checkpoint's weights, loaded above)
+                ema.load_state_dict(state.get("eager_ema") or {})
             if graph:  # the rate of a capturable Adam is a device tensor (load_state_dict brought the saved copy)
                 for g_ in optimizer.param_groups:
                     g_["lr"] = torch.tensor(float(g_["lr"]), device="cuda")
@@ -463,6 +484,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                         if clip:
                             grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), float(max_grad_norm))
                         optimizer.step()
+                    if use_ema:
+                        ema.update(applied)
                     optimizer.zero_grad()
                 if applied:
                     ep_train_losses.append(loss["nmse"].item())  # train_auto.py:260
@@ -513,8 +536,9 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             ckpt_dir = output_dir / f"ckpt-{ep}"
             if rank == 0:
                 ckpt_dir.mkdir(exist_ok=True, parents=True)
-            result = evaluate(model, dev_data, ckpt_dir, batch_size=eval_batch_size, plot_interval=plot_interval,
-                              device_loader=device_loader, sharded=world > 1)
+            with averaged_weights(ema if ema_eval else None):  # (--ema_eval 1: validation on the averaged weights)
+                result = evaluate(model, dev_data, ckpt_dir, batch_size=eval_batch_size, plot_interval=plot_interval,
+                                  device_loader=device_loader, sharded=world > 1)
         if (ep + 1) % eval_interval == 0 and rank == 0:
             dev_scores = result["scores"]
             dump_json(dev_scores, ckpt_dir / "dev_scores.json")
@@ -525,6 +549,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             # bare state_dict with the reference's key names (train_auto.py:301); cloned because under the fused engine
             # the parameters are float/complex views of ONE flat buffer, which torch.save refuses to serialise as is
             torch.save({k: v.detach().clone() for k, v in model.state_dict().items()}, ckpt_path)
+            if use_ema:  # the averaged weights beside it, same keys: load_ckpt / --init_from / test_multistep --use_ema 1 read it
+                torch.save({k: v.cpu() for k, v in ema.ema_state_dict().items()}, ckpt_dir / "model_ema.pt")
             dump_json(dict(ep=ep, train_loss=float(np.mean(ep_train_losses)), dev_loss=float(np.mean(dev_scores["all"]["nmse"])),
                            time=time.time() - ep_start_time), ckpt_dir / "scores.json")
             # full training state next to the reference's artefacts (written last, atomically: a crash mid-checkpoint
@@ -538,7 +564,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                             optimizer=opt_state, scheduler=schedule.state_dict(), early_stopping=stopper.state_dict(),
                             rng=torch.get_rng_state(), fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach),
                             model_extra=model.extra_train_state() if hasattr(model, "extra_train_state") else None,
-                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {})), tmp)
+                            **(dict(skipped_steps=guard.skipped) if guard.enabled else {}),
+                            **(dict(eager_ema=ema.state_dict()) if use_ema and engine is None else {})), tmp)
             tmp.replace(state_path)
         else:
             stop = False
@@ -596,10 +623,12 @@ def main(argv=None):
               gradient_accumulation_steps=args.fused_accumulation_steps if args.fused else args.gradient_accumulation_steps,
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
               unroll_detach=bool(args.unroll_detach), optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
-              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips)
+              init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips,
+              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval))
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
-        load_best_ckpt(model, output_dir)
+        # (--ema_eval 1: the run chose its best checkpoint by the averaged weights' dev loss; the test runs on those weights)
+        load_best_ckpt(model, output_dir, use_ema=bool(args.ema_eval))
         test(model, test_data, output_dir / "test", batch_size=1, infer_steps=20, plot_interval=10)
     if world > 1:
         dist.barrier()

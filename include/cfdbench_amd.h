@@ -653,7 +653,32 @@ int cfd_fno_backward_phase_ex(const cfd_plan* plan, const cfd_fno_shape* shape, 
  *                          moments, gradient buffer and clip[0..1] are bitwise those of the call without the bit.
  *                          Together with CFD_STEP_ACCUMULATE the bit is IGNORED: no norm is taken there, a non-finite micro-batch makes
  *                          the accumulator non-finite, and the optimiser call on the accumulator with the bit skips the whole group.
- *                          No launch more than clipping costs (k_gradsq).                                                             */
+ *                          No launch more than clipping costs (k_gradsq).
+ *
+ * An exponential moving average (EMA) of the weights inside the optimiser launch (FnoTrainEngine(ema_decay=d)) -- no bit of `flags` and no
+ * struct field, but ONE MORE ENTRY POINT, cfd_fno_adam_step_ema: the 25 arguments of cfd_fno_adam_step in the same order, then
+ * `float* ema, float ema_decay`.  cfd_fno_adam_step forwards to it with ema = NULL, so with ema == NULL the two are the same call, bit for
+ * bit.  With ema != NULL:
+ *   - ema holds n floats laid out like `param`, on any 4-byte boundary (a 16-byte-aligned `param` with a 4-byte-aligned `ema` runs the
+ *     scalar form, with the same bits); the caller initialises it, usually as a copy of the initial weights;
+ *   - 0 <= ema_decay < 1; anything else, a NaN included, is CFD_ERR_INVALID_ARG before any launch;
+ *   - RULE, the ema.mul_(d).add_(p, alpha = 1 - d) of timm and diffusers, applied to the parameter the step has just produced while it is
+ *     still in a register:
+ *         ema[i] = fmaf(d, ema[i], q),   q = fp32((1.f - d) * param_new[i]),   d = ema_decay               i < n
+ *     ROUNDING ORDER: 1.f - d is formed in fp32, the product q is rounded on its own, the fmaf rounds once more -- two roundings of a
+ *     convex combination, so the result lies within 2^-23 * max(|ema[i]|, |param_new[i]|) of the exact d e + (1 - d) p taken with the fp32
+ *     d and 1.f - d.  ema_decay = 0 gives ema[i] == param_new[i] bit for bit for any finite ema[i], except the sign of a zero
+ *     (fmaf(0, e, -0.f) is +0.f).  Elements that belong to no tensor
+ *     (alignment padding) are averaged like any other;
+ *   - param, exp_avg, exp_avg_sq, the gradient buffer and the clip buffer are bitwise those of the call without `ema`, with every
+ *     combination of CFD_TRAIN_DEFER_*, CFD_STEP_DECOUPLED_WD, grads->clip and CFD_STEP_SKIP_NONFINITE; under CFD_TRAIN_DEFER_STEM the fc0
+ *     rows of the average are updated by the workgroups that finish those rows;
+ *   - SKIP: a step skipped under CFD_STEP_SKIP_NONFINITE returns before any element is loaded, so ema keeps every bit, a NaN the caller
+ *     left there included.  The decay of a step is the caller's, by value, like `step`;
+ *   - with CFD_STEP_ACCUMULATE both arguments are IGNORED (no parameter is written there), as CFD_STEP_DECOUPLED_WD is;
+ *   - n == 0: nothing of ema is read or written.
+ * 8 more bytes per element than the call without `ema` (one more load and one more store: 36 bytes instead of 28), and NO launch more: the
+ * launch count is that of the call without `ema`.  cfd_adam_flat and cfd_adam_multi have no such form.                              */
 #define CFD_TRAIN_DEFER_SCALE 1
 #define CFD_TRAIN_DEFER_HEAD 2
 #define CFD_TRAIN_DEFER_STEM 4
@@ -673,6 +698,11 @@ int cfd_fno_adam_step(const cfd_plan* plan, const cfd_fno_shape* shape, const cf
                       const float* inputs, const float* case_params, const float* mask, const float* sums, void* ws, float* param,
                       float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
                       float weight_decay, int step, float grad_scale, int which, int act_dtype, int flags, void* stream);
+int cfd_fno_adam_step_ema(const cfd_plan* plan, const cfd_fno_shape* shape, const cfd_fno_params* params, const cfd_fno_params* grads,
+                          const float* inputs, const float* case_params, const float* mask, const float* sums, void* ws, float* param,
+                          float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int step, float grad_scale, int which, int act_dtype, int flags, void* stream, float* ema,
+                          float ema_decay);
 
 /* grads: same layout as params, every tensor overwritten.  coef/gpreds_ext as in cfd_fno_head_bwd.  grads->d_inputs /
  * grads->d_case_params (cfd_fno_params, ABI 603; NULL = not asked): the gradients with respect to `inputs` and `case_params`, written by
