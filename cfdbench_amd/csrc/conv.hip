@@ -12,6 +12,7 @@
 //             P^T folds the pad ring back onto the border pixels (k_fold_pad) -- deterministic, no atomics
 //   weight gradient: gw[o][(i,ky,kx)] = sum_p g[o][p] * in[i][clamp(...)]                    M = Cout, N = Cin*k*k, K = pixels
 #include "cfd_conv.h"
+#include "cfd_launch.h"
 
 #define CV_WAVES 4
 
@@ -168,20 +169,14 @@ static int launch_conv_gather(const float* src, const float* w, const float* bia
     if (mtw == 5) mtw = 6;
     if (mtw > 6 && mtw < 12) mtw = 8;
     const int mgroups = (MT + mtw - 1) / mtw;
-#define CV_L(M_) hipLaunchKernelGGL((k_conv_gather<M_, EXT>), dim3((unsigned)blocks, mgroups), dim3(64 * CV_WAVES), 0, st, src, w, bias, dst, g, tiles_per_b, total)
-    switch (mtw) {
-        case 1: CV_L(1); break;
-        case 2: CV_L(2); break;
-        case 3: CV_L(3); break;
-        case 4: CV_L(4); break;
-        case 6: CV_L(6); break;
-        case 8: CV_L(8); break;
-        case 12: CV_L(12); break;
-        default:
-            cfd_set_error("%s: %d output channels unsupported (max 192)", what, Cm);
-            return CFD_ERR_UNSUPPORTED;
+    if (mtw > 12) {  // (M tiles per wave after the rounding above: 1 2 3 4 6 8 12)
+        cfd_set_error("%s: %d output channels unsupported (max 192)", what, Cm);
+        return CFD_ERR_UNSUPPORTED;
     }
-#undef CV_L
+    cfd_dispatch([&](auto M) {
+        hipLaunchKernelGGL((k_conv_gather<CFD_I(M), EXT>), dim3((unsigned)blocks, mgroups), dim3(64 * CV_WAVES), 0, st, src, w, bias, dst, g,
+                           tiles_per_b, total);
+    }, cfd_among<1, 2, 3, 4, 6, 8, 12>(mtw));
     CFD_LAUNCH_CHECK(what);
     return CFD_OK;
 }
@@ -549,9 +544,9 @@ CfdPartReduceJob cfd_conv_part_reduce_job(const float* part, float* out, long n,
 
 void cfd_conv_part_reduce(const float* part, float* out, long n, int nchunk, hipStream_t st, float* out2, long n1) {
     const CfdPartReduceJob j = cfd_conv_part_reduce_job(part, out, n, nchunk, out2, n1);
-    if (j.G == 16) hipLaunchKernelGGL((k_part_reduce<16>), dim3((unsigned)j.nblk), dim3(256), 0, st, part, out, n, nchunk, out2, j.n1);
-    else if (j.G == 4) hipLaunchKernelGGL((k_part_reduce<4>), dim3((unsigned)j.nblk), dim3(256), 0, st, part, out, n, nchunk, out2, j.n1);
-    else hipLaunchKernelGGL((k_part_reduce<1>), dim3((unsigned)j.nblk), dim3(256), 0, st, part, out, n, nchunk, out2, j.n1);
+    cfd_dispatch([&](auto G) {
+        hipLaunchKernelGGL((k_part_reduce<CFD_I(G)>), dim3((unsigned)j.nblk), dim3(256), 0, st, part, out, n, nchunk, out2, j.n1);
+    }, cfd_among<16, 4, 1>(j.G));
 }
 
 // per-channel sum over (B, HW) in two parallel stages (defined next to the BatchNorm reductions it shares)

@@ -16,6 +16,7 @@
 //     innermost, so a column tile is ONE tap and its B operand one aligned read; the four waves split the K steps of a 16-pixel
 //     tile and are summed through LDS at the end (fixed order).
 #include "cfd_conv.h"
+#include "cfd_launch.h"
 
 typedef cfd_u32x4 u4;
 
@@ -571,28 +572,21 @@ size_t cfd_conv6_ws_bytes(const ConvGeom& g, bool ext) {
 }
 
 template <int KS, int CC, bool EXT>
-static void conv6_launch(const Conv6Plan& P, const float* src, const u4* wfrag, const float* bias, float* dst, const ConvGeom& g,
-                         float* gin_direct, float* stats, hipStream_t st) {
+static int conv6_launch(const Conv6Plan& P, const float* src, const u4* wfrag, const float* bias, float* dst, const ConvGeom& g,
+                        float* gin_direct, float* stats, hipStream_t st, const char* what) {
     const dim3 grid((unsigned)P.gx, P.mgroups, P.ksplit);
-#define C6_L(M_, N_, S_)                                                                                                          \
-    do {                                                                                                                          \
-        static bool attr_set = false;                                                                                             \
-        if (!attr_set) {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)k_conv6<KS, M_, CC, EXT, N_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-            attr_set = true;                                                                                                      \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((k_conv6<KS, M_, CC, EXT, N_, S_>), grid, dim3(256), P.lds, st, src, wfrag, bias, dst, g, P.t, P.MTall, \
-                           (int)P.ptiles, gin_direct, stats);                                                                     \
-    } while (0)
-    if constexpr (!EXT && KS == 3) {
-        if (stats) {  // (conv6_run: NI == 3, one pass)
-            if (P.mtw == 1) C6_L(1, 3, true); else C6_L(2, 3, true);
-            return;
+    // M tiles per wave, fragments in flight, S: the batch-norm statistics ride (conv6_run: forward 3 x 3, NI == 3, one pass)
+    const bool st3 = !EXT && KS == 3 && stats;
+    int rc = CFD_OK;
+    cfd_dispatch([&](auto M, auto N, auto S) {
+        if constexpr (!CFD_B(S) || (!EXT && KS == 3 && CFD_I(N) == 3)) {
+            rc = cfd_allow_lds<k_conv6<KS, CFD_I(M), CC, EXT, CFD_I(N), CFD_B(S)>>(150 * 1024, what);
+            if (rc != CFD_OK) return;
+            hipLaunchKernelGGL((k_conv6<KS, CFD_I(M), CC, EXT, CFD_I(N), CFD_B(S)>), grid, dim3(256), P.lds, st, src, wfrag, bias, dst, g, P.t,
+                               P.MTall, (int)P.ptiles, gin_direct, stats);
         }
-    }
-    if (P.mtw == 1) { if (P.NI == 3) C6_L(1, 3, false); else C6_L(1, 5, false); }
-    else { if (P.NI == 3) C6_L(2, 3, false); else C6_L(2, 5, false); }
-#undef C6_L
+    }, cfd_among<1, 2>(P.mtw), cfd_among<3, 5>(st3 || P.NI == 3 ? 3 : 5), st3);
+    return rc;
 }
 
 template <bool EXT>
@@ -616,12 +610,12 @@ static int conv6_run(const float* src, const float* w, const float* bias, float*
     if (EXT && g.zpad && !gd) return CFD_ERR_UNSUPPORTED;  // (zero padding has no fold pass: callers ask cfd_conv6_zeropad_covers first)
     if (stats && (EXT || g.ks != 3 || P.ksplit > 1 || P.NI != 3)) return CFD_ERR_UNSUPPORTED;  // (callers ask cfd_conv6_stats_slots first)
     if (g.ks == 3) {
-        if (P.CC == 8) conv6_launch<3, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st);
-        else conv6_launch<3, 16, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st);
+        if (P.CC == 8) CFD_TRY((conv6_launch<3, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st, what)));
+        else CFD_TRY((conv6_launch<3, 16, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st, what)));
     } else if (g.ks == 5) {  // (round 4: the 5 x 5 convolutions of the Auto-DeepONet-CNN branch, src/models/auto_deeponet_cnn.py:17-33)
-        conv6_launch<5, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st);
+        CFD_TRY((conv6_launch<5, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st, what)));
     } else {
-        conv6_launch<7, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st);
+        CFD_TRY((conv6_launch<7, 8, EXT>(P, src, wfrag, bias, kdst, g, gd, stats, st, what)));
     }
     CFD_LAUNCH_CHECK(what);
     if (P.ksplit > 1) {
@@ -949,27 +943,14 @@ int cfd_conv6_wgrad(const float* gout, const float* in, float* gw, float* gb, vo
     const Wg6Plan P = wg6_plan(g);
     if (!P.ok) return CFD_ERR_UNSUPPORTED;
     const dim3 grid(P.groups, P.chunks, P.mgroups * P.nkg);
-#define W6_L(K_, M_, Y_)                                                                                                          \
-    do {                                                                                                                          \
-        static bool attr_set = false;                                                                                             \
-        if (!attr_set) {                                                                                                          \
-            (void)hipFuncSetAttribute((const void*)k_conv6_wgrad<K_, M_, Y_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-            attr_set = true;                                                                                                      \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((k_conv6_wgrad<K_, M_, Y_>), grid, dim3(256), P.lds, st, gout, in, (float*)ws, g, P.t, P.ntiles,        \
-                           gb ? 1 : 0);                                                                                           \
-    } while (0)
-    if (g.ks == 3) {
-        if (P.mtw == 1) W6_L(3, 1, 3);
-        else W6_L(3, 2, 3);
-    } else if (g.ks == 5) {
-        if (P.mtw == 1) W6_L(5, 1, 2);
-        else W6_L(5, 2, 2);
-    } else {
-        if (P.mtw == 1) W6_L(7, 1, 2);
-        else W6_L(7, 2, 2);
-    }
-#undef W6_L
+    int rc = CFD_OK;
+    cfd_dispatch([&](auto K, auto M) {
+        constexpr int Y = CFD_I(K) == 3 ? 3 : 2;
+        rc = cfd_allow_lds<k_conv6_wgrad<CFD_I(K), CFD_I(M), Y>>(150 * 1024, what);
+        if (rc != CFD_OK) return;
+        hipLaunchKernelGGL((k_conv6_wgrad<CFD_I(K), CFD_I(M), Y>), grid, dim3(256), P.lds, st, gout, in, (float*)ws, g, P.t, P.ntiles, gb ? 1 : 0);
+    }, cfd_among<3, 5, 7>(g.ks), cfd_among<1, 2>(P.mtw));
+    CFD_TRY(rc);
     CFD_LAUNCH_CHECK(what);
     const long n1 = (long)g.Co * g.Ci * g.ks * g.ks;
     if (defer) {

@@ -7,6 +7,7 @@
 // one LDS-tiled kernel C = epi(op(A) op(B)): 64x64 block tile, 4 waves x (2x2) MFMA tiles, K in slabs of 16 that are
 // prefetched into registers while the previous slab is on the matrix pipe.
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include <type_traits>
 
 #define GT 64   // block tile edge (M and N) of the small-problem kernel: 4 waves x (2 x 2) MFMA tiles
@@ -345,38 +346,27 @@ static int launch_gemm(const float* A, const float* B, float* C, int M, int N, i
     const int ldk = splits > 1 ? N : ldc;
     {
         CFD_PROF_W("k_gemm", st, 4.0 * ((double)M * K + (double)K * N + (double)M * N), 2.0 * M * (double)N * K);
-#define GEMM_K(AT_, BT_, G_, TM_, TN_, NW_)                                                                                                \
-    do {                                                                                                                                  \
-        constexpr int bm_ = 16 * TM_ * G_, bn_ = 16 * TN_ * (NW_ / G_);                                                                   \
-        constexpr size_t lds_ = 2 * sizeof(float) * (SlabRegs<!AT_, bm_ / 64>::FLOATS + SlabRegs<BT_, bn_ / 64>::FLOATS);                \
-        static bool attr_set = false;                                                                                                     \
-        if (!attr_set) {                                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)k_gemm<AT_, BT_, G_, TM_, TN_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-            attr_set = true;                                                                                                              \
-        }                                                                                                                                 \
-        hipLaunchKernelGGL((k_gemm<AT_, BT_, G_, TM_, TN_, NW_>), grid, dim3(64 * NW_), lds_, st, A, B, Ck, M, N, K, lda, ldb, ldk, ek, per, nbx,   \
-                           nby, splits);                                                                                                  \
-    } while (0)
-#define GEMM_L(AT_, BT_)                                  \
-    do {                                                  \
-        if (kind == 64) GEMM_K(AT_, BT_, 2, 2, 2, 4);        \
-        else if (kind == 128) GEMM_K(AT_, BT_, 2, 4, 4, 4);  \
-        else if (kind == 8) GEMM_K(AT_, BT_, 4, 2, 2, 8);    \
-        else if (kind == 1) GEMM_K(AT_, BT_, 4, 2, 8, 4);    \
-        else GEMM_K(AT_, BT_, 4, 2, 16, 4);                  \
-    } while (0)
         if (ek.ones1) {  // (the weight-gradient form with its bias column: 64 x 64 blocks only)
             CFD_REQUIRE(at && !bt && kind == 64, CFD_ERR_UNSUPPORTED, "%s: the ones column rides in the A^T B form on 64 x 64 blocks only", what);
             constexpr size_t lds1 = 2 * sizeof(float) * (SlabRegs<false, 1>::FLOATS + SlabRegs<false, 1>::FLOATS);
             hipLaunchKernelGGL((k_gemm<true, false, 2, 2, 2, 4, true>), grid, dim3(256), lds1, st, A, B, Ck, M, N, K, lda, ldb, ldk, ek, per, nbx,
                                nby, splits);
+        } else {
+            int rc = CFD_OK;
+            cfd_dispatch([&](auto AT, auto BT, auto KIND) {
+                // block shape of a tile kind: wave groups G, 16-row / 16-column tiles per wave TM x TN, waves NW
+                constexpr int kd = CFD_I(KIND);
+                constexpr int G = kd == 64 || kd == 128 ? 2 : 4, TM = kd == 128 ? 4 : 2, TN = kd == 64 || kd == 8 ? 2 : kd == 128 ? 4 : kd == 1 ? 8 : 16;
+                constexpr int NW = kd == 8 ? 8 : 4;
+                constexpr int bm_ = 16 * TM * G, bn_ = 16 * TN * (NW / G);
+                constexpr size_t lds_ = 2 * sizeof(float) * (SlabRegs<!CFD_B(AT), bm_ / 64>::FLOATS + SlabRegs<CFD_B(BT), bn_ / 64>::FLOATS);
+                rc = cfd_allow_lds<k_gemm<CFD_B(AT), CFD_B(BT), G, TM, TN, NW>>(80 * 1024, what);
+                if (rc != CFD_OK) return;
+                hipLaunchKernelGGL((k_gemm<CFD_B(AT), CFD_B(BT), G, TM, TN, NW>), grid, dim3(64 * NW), lds_, st, A, B, Ck, M, N, K, lda, ldb, ldk, ek,
+                                   per, nbx, nby, splits);
+            }, at != 0, bt != 0, cfd_among<64, 128, 8, 1, 2>(kind));
+            CFD_TRY(rc);
         }
-        else if (!at && !bt) GEMM_L(false, false);
-        else if (!at && bt) GEMM_L(false, true);
-        else if (at && !bt) GEMM_L(true, false);
-        else GEMM_L(true, true);
-#undef GEMM_L
-#undef GEMM_K
     }
     CFD_LAUNCH_CHECK(what);
     if (splits > 1) {
@@ -586,26 +576,23 @@ static int rowgemm6_run(const float* A, int lda, const float* W, int ldw, bool t
     const unsigned total = (unsigned)nks * NTall * 64;
     unsigned pb = (total + 255) / 256;
     if (pb > 512) pb = 512;
-    if (trans) hipLaunchKernelGGL((k_rowgemm6_prep<true>), dim3(pb), dim3(256), 0, st, W, ldw, (r6_u4*)frag_ws, N, K, NTall, nks);
-    else hipLaunchKernelGGL((k_rowgemm6_prep<false>), dim3(pb), dim3(256), 0, st, W, ldw, (r6_u4*)frag_ws, N, K, NTall, nks);
+    with_bools([&](auto T) {
+        hipLaunchKernelGGL((k_rowgemm6_prep<CFD_B(T)>), dim3(pb), dim3(256), 0, st, W, ldw, (r6_u4*)frag_ws, N, K, NTall, nks);
+    }, trans);
     CFD_LAUNCH_CHECK(what);
     CFD_PROF_W("k_rowgemm6", st, 4.0 * ((double)M * K + (double)K * N + (double)M * N), 2.0 * M * (double)N * K);
-#define R6_LAUNCH(NT_, RT_, NB_)                                                                                                         \
-    do {                                                                                                                                 \
-        constexpr size_t lds = NB_ * (size_t)NT_ * 192 * sizeof(r6_u4);                                                                  \
-        static bool attr_set = false;                                                                                                    \
-        if (!attr_set) {                                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)k_rowgemm6<NT_, RT_, NB_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-            attr_set = true;                                                                                                             \
-        }                                                                                                                                \
-        hipLaunchKernelGGL((k_rowgemm6<NT_, RT_, NB_>), dim3((unsigned)((M + 64 * RT_ - 1) / (64 * RT_))), dim3(256), lds, st, A, lda,        \
-                           (const r6_u4*)frag_ws, C, ldc, M, N, K, epi, NTall, nks);                                                     \
-    } while (0)
     // light shapes (one row tile per wave, four workgroups per CU): the product is memory-bound and its phases do not overlap inside a
     // workgroup -- 131 k x 200 x 200: 86 us on <13, 1, 1> against 118 on the first shape (two row tiles per wave, 235 VGPRs, two per CU)
-    if (NTall <= 7) R6_LAUNCH(7, 1, 2);
-    else R6_LAUNCH(R6_NT, 1, 1);
-#undef R6_LAUNCH
+    int rc = CFD_OK;
+    cfd_dispatch([&](auto NT) {  // (column tiles per pass; the seven-tile shape double-buffers its fragments)
+        constexpr int RT = 1, NB = CFD_I(NT) == 7 ? 2 : 1;
+        constexpr size_t lds = NB * (size_t)CFD_I(NT) * 192 * sizeof(r6_u4);
+        rc = cfd_allow_lds<k_rowgemm6<CFD_I(NT), RT, NB>>(lds, what);
+        if (rc != CFD_OK) return;
+        hipLaunchKernelGGL((k_rowgemm6<CFD_I(NT), RT, NB>), dim3((unsigned)((M + 64 * RT - 1) / (64 * RT))), dim3(256), lds, st, A, lda,
+                           (const r6_u4*)frag_ws, C, ldc, M, N, K, epi, NTall, nks);
+    }, cfd_among<7, R6_NT>(NTall <= 7 ? 7 : R6_NT));
+    CFD_TRY(rc);
     CFD_LAUNCH_CHECK(what);
     return CFD_OK;
 }
@@ -777,11 +764,7 @@ static int roww6_run(const float* gz, const float* x, float* gw, float* gb, void
     CFD_REQUIRE(nchunk <= chunks, CFD_ERR_WORKSPACE, "%s: %d row chunks planned, %d launched", what, chunks, nchunk);  // (the workspace is sized by `chunks`)
     const dim3 grid((unsigned)nchunk, (unsigned)((Kx + 16 * W6_KT - 1) / (16 * W6_KT)), (unsigned)((N + 16 * W6_NT - 1) / (16 * W6_NT)));
     constexpr size_t lds = (size_t)(W6_NT + W6_KT) * 192 * sizeof(r6_u4);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_rowwgrad6, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    CFD_TRY(cfd_allow_lds<k_rowwgrad6>(lds, what));
     CFD_PROF_W("k_rowwgrad6", st, 4.0 * ((double)M * K + (double)M * N + (double)N * K), 2.0 * M * (double)N * K);
     hipLaunchKernelGGL(k_rowwgrad6, grid, dim3(256), lds, st, gz, x, (float*)ws, M, N, K, Kx, rpc);
     CFD_LAUNCH_CHECK(what);

@@ -13,6 +13,7 @@
 // not fit together (full modes above about 106 x 106).  Every output element is one accumulator chain over k ascending in steps of 4
 // whatever the split, so the split changes no result bit.
 #include "cfd_common.h"
+#include "cfd_launch.h"
 
 #define CFD_MANY_LDS_CAP 163840    // dynamic LDS a workgroup may ask for: the 160 KB of a CU
 #define CFD_MANY_LDS_HALF 81920    // two workgroups per CU
@@ -310,14 +311,6 @@ __global__ __launch_bounds__(256) void k_idft_many(const float2* __restrict__ z,
 
 static int many_blocks(long items) { return items < CFD_MANY_BLOCKS ? (int)items : CFD_MANY_BLOCKS; }
 
-template <typename K>
-static void many_lds_attr(K kern, size_t lds, size_t& set) {  // > 64 KB of dynamic LDS needs the attribute (once per size per kernel)
-    if (lds > 64 * 1024 && lds > set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        set = lds;
-    }
-}
-
 int cfd_int_dft_many(const cfd_plan* p, const float* x, float* xh, int nimg, int act_in, void* stream) {
     CFD_REQUIRE(p && p->many && p->d_many_fwd, CFD_ERR_INVALID_ARG, "cfd_spectral_dft: not a many-modes plan");
     if (nimg == 0) return CFD_OK;
@@ -329,33 +322,16 @@ int cfd_int_dft_many(const cfd_plan* p, const float* x, float* xh, int nimg, int
     CFD_PROF_W(act_in ? "k_dft_many_act" : "k_dft_many", st, (double)nimg * (4.0 * p->H * p->W + 16.0 * p->m1 * p->m2),
                (double)nimg * (4.0 * p->H * p->W * p->m2 + 16.0 * p->H * p->m1 * p->m2));
     const int blocks = many_blocks((long)nimg * c.G);
-    static size_t set0 = 0, set1 = 0;
-    if (act_in) {
-        many_lds_attr(k_dft_many<true>, c.lds, set1);
-        hipLaunchKernelGGL(k_dft_many<true>, dim3(blocks), dim3(256), c.lds, st, x, (float2*)xh, (const float*)p->d_many_fwd, nimg, p->H, p->W,
+    int rc = CFD_OK;
+    with_bools([&](auto A) {
+        rc = cfd_allow_lds<k_dft_many<CFD_B(A)>>(c.lds, "cfd_spectral_dft");
+        if (rc != CFD_OK) return;
+        hipLaunchKernelGGL(k_dft_many<CFD_B(A)>, dim3(blocks), dim3(256), c.lds, st, x, (float2*)xh, (const float*)p->d_many_fwd, nimg, p->H, p->W,
                            p->m1, p->m2, c.RB, c.G, c.nlg, c.ioff, c.nc);
-    } else {
-        many_lds_attr(k_dft_many<false>, c.lds, set0);
-        hipLaunchKernelGGL(k_dft_many<false>, dim3(blocks), dim3(256), c.lds, st, x, (float2*)xh, (const float*)p->d_many_fwd, nimg, p->H, p->W,
-                           p->m1, p->m2, c.RB, c.G, c.nlg, c.ioff, c.nc);
-    }
+    }, act_in != 0);
+    CFD_TRY(rc);
     CFD_LAUNCH_CHECK("cfd_spectral_dft(many modes)");
     return CFD_OK;
-}
-
-template <int EPI>
-static void many_launch_inv(const ManyInvCfg& c, int blocks, hipStream_t st, const float2* z, const float* addend, const float* aprev, float* out,
-                            const float* tab, int nimg, const cfd_plan* p) {
-    static size_t set0 = 0, set1 = 0;
-    if (c.tbl) {
-        many_lds_attr(k_idft_many<EPI, true>, c.lds, set1);
-        hipLaunchKernelGGL((k_idft_many<EPI, true>), dim3(blocks), dim3(256), c.lds, st, z, addend, aprev, out, tab, nimg, p->H, p->W, p->m1, p->m2,
-                           c.RB);
-    } else {
-        many_lds_attr(k_idft_many<EPI, false>, c.lds, set0);
-        hipLaunchKernelGGL((k_idft_many<EPI, false>), dim3(blocks), dim3(256), c.lds, st, z, addend, aprev, out, tab, nimg, p->H, p->W, p->m1, p->m2,
-                           c.RB);
-    }
 }
 
 int cfd_int_idft_many(const cfd_plan* p, const float* z, const float* addend, const float* aprev, float* out, int nimg, int epi, void* stream) {
@@ -374,9 +350,14 @@ int cfd_int_idft_many(const cfd_plan* p, const float* z, const float* addend, co
     const float2* zz = (const float2*)z;
     const float* tab = (const float*)p->d_many_inv;
     const int blocks = many_blocks(items);
-    if (epi == 0) many_launch_inv<0>(c, blocks, st, zz, addend, aprev, out, tab, nimg, p);
-    else if (epi == 1) many_launch_inv<1>(c, blocks, st, zz, addend, aprev, out, tab, nimg, p);
-    else many_launch_inv<2>(c, blocks, st, zz, addend, aprev, out, tab, nimg, p);
+    int rc = CFD_OK;
+    cfd_dispatch([&](auto E, auto T) {
+        rc = cfd_allow_lds<k_idft_many<CFD_I(E), CFD_B(T)>>(c.lds, "cfd_spectral_idft");
+        if (rc != CFD_OK) return;
+        hipLaunchKernelGGL((k_idft_many<CFD_I(E), CFD_B(T)>), dim3(blocks), dim3(256), c.lds, st, zz, addend, aprev, out, tab, nimg, p->H, p->W,
+                           p->m1, p->m2, c.RB);
+    }, cfd_among<0, 1, 2>(epi), (bool)c.tbl);
+    CFD_TRY(rc);
     CFD_LAUNCH_CHECK("cfd_spectral_idft(many modes)");
     return CFD_OK;
 }

@@ -8,6 +8,7 @@
 // step at B=256), and fp32 MFMA on gfx950 only matches the VALU's fp32 rate without overlapping it, so the GEMMs run
 // as split-bf16 3-term products on v_mfma_f32_16x16x32_bf16 (cfd_common.h, relative error ~2^-16, fp32 accumulate).
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"
 
 #define HEAD_HD 128
@@ -349,6 +350,9 @@ static int head_check(const char* fn, int B, int C, int Hd, int Co, int HW) {
     return CFD_OK;
 }
 
+// channels per lane group of the K = 32 operand (CQ / KS of the kernels): the bucket of a hidden width
+static cfd_among_t<2, 5, 8> head_cq(int C) { return {C <= 8 ? 2 : C <= 20 ? 5 : 8}; }
+
 // launchers of the channel route (out_chan 3 .. 8; defined behind its kernels at the end of this file)
 static int head_fwd_co(const float* a, const float* mask, const float* label, const float* w1, const float* b1, const float* w2,
                        const float* b2, float* preds, float* sums, void* ws, int B, int C, int Co, int HW, int act_in, hipStream_t st,
@@ -386,33 +390,12 @@ int cfd_int_fno_head_fwd(const void* a_, const float* mask, const float* label, 
     {
     CFD_PROF_W("k_head_fwd", st, B * HW * ((double)cfd_dt_size(dt) * C + 4.0 * (1 + (label ? 2 : 1) * Co)), 2.0 * B * HW * (double)HEAD_HD * (C + Co));
     const bool ap3 = dt == CFD_DT_F32 && cfd_act_pieces() == 3;  // fp32-exact-class route (bf16 storage keeps two pieces)
-#define CFD_HF_P(Q_, V_, A_, T_, P_)                                                                                      \
-    hipLaunchKernelGGL((k_head_fwd<Q_, V_, A_, T_, P_>), dim3(blocks), dim3(256), 0, st, (const T_*)a_, mask, label, w1, b1, w2, \
-                       b2, preds, part, B, C, Co, HW)
-#define CFD_HF(Q_, V_, A_, T_)                                                                        \
-    do {                                                                                              \
-        if constexpr (sizeof(T_) == 4) { if (ap3) CFD_HF_P(Q_, V_, A_, T_, 3); else CFD_HF_P(Q_, V_, A_, T_, 2); } \
-        else CFD_HF_P(Q_, V_, A_, T_, 2);                                                             \
-    } while (0)
-#define CFD_HF_Q(Q_)                                         \
-    do {                                                     \
-        if (dt == CFD_DT_BF16) {                             \
-            if (act_in) CFD_HF(Q_, false, true, __bf16);     \
-            else CFD_HF(Q_, false, false, __bf16);           \
-        } else if (v4) {                                     \
-            if (act_in) CFD_HF(Q_, true, true, float);       \
-            else CFD_HF(Q_, true, false, float);             \
-        } else {                                             \
-            if (act_in) CFD_HF(Q_, false, true, float);      \
-            else CFD_HF(Q_, false, false, float);            \
-        }                                                    \
-    } while (0)
-    if (C <= 8) CFD_HF_Q(2);  // channels per lane group of the K = 32 operand
-    else if (C <= 20) CFD_HF_Q(5);
-    else CFD_HF_Q(8);
-#undef CFD_HF_Q
-#undef CFD_HF
-#undef CFD_HF_P
+    cfd_dispatch([&](auto Q, auto T, auto V, auto A, auto P) {
+        using TA = CFD_T(T);
+        if constexpr (sizeof(TA) == 4 || (!CFD_B(V) && CFD_I(P) == 2))
+            hipLaunchKernelGGL((k_head_fwd<CFD_I(Q), CFD_B(V), CFD_B(A), TA, CFD_I(P)>), dim3(blocks), dim3(256), 0, st, (const TA*)a_, mask, label,
+                               w1, b1, w2, b2, preds, part, B, C, Co, HW);
+    }, head_cq(C), cfd_storage(dt), v4, act_in != 0, cfd_among<3, 2>(ap3 ? 3 : 2));
     }
     CFD_LAUNCH_CHECK("cfd_fno_head_fwd");
     if (label) {
@@ -1622,24 +1605,10 @@ extern "C" int cfd_fno_head_bwd(const float* a, const float* mask, const float* 
     const bool v4 = HW % 4 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)ga % 16) == 0;
     {
     CFD_PROF_W("k_head_bwd", st, 4.0 * B * HW * (2.0 * C + 1 + 2.0 * Co), 2.0 * B * HW * (double)HEAD_HD * (3.0 * C + 2.0 * Co));
-    const bool ap3 = cfd_act_pieces() == 3;
-#define CFD_HB_P(K_, V_, A_, P_)                                                                                   \
-    hipLaunchKernelGGL((k_head_bwd<K_, V_, A_, false, float, P_>), dim3(blocks), dim3(256), 0, st, a, mask, label, preds, gpreds_ext, \
-                       coef, w1, b1, w2, ga, part, B, C, Co, HW, (float*)nullptr, (const float*)nullptr, 0.f, 0.f)
-#define CFD_HB(K_, V_, A_) do { if (ap3) CFD_HB_P(K_, V_, A_, 3); else CFD_HB_P(K_, V_, A_, 2); } while (0)
-#define CFD_HB_VA(K_)                              \
-    do {                                           \
-        if (v4 && act_in) CFD_HB(K_, true, true);  \
-        else if (v4) CFD_HB(K_, true, false);      \
-        else if (act_in) CFD_HB(K_, false, true);  \
-        else CFD_HB(K_, false, false);             \
-    } while (0)
-    if (C <= 8) CFD_HB_VA(2);
-    else if (C <= 20) CFD_HB_VA(5);
-    else CFD_HB_VA(8);
-#undef CFD_HB_VA
-#undef CFD_HB
-#undef CFD_HB_P
+    cfd_dispatch([&](auto K, auto V, auto A, auto P) {
+        hipLaunchKernelGGL((k_head_bwd<CFD_I(K), CFD_B(V), CFD_B(A), false, float, CFD_I(P)>), dim3(blocks), dim3(256), 0, st, a, mask, label, preds,
+                           gpreds_ext, coef, w1, b1, w2, ga, part, B, C, Co, HW, (float*)nullptr, (const float*)nullptr, 0.f, 0.f);
+    }, head_cq(C), v4, act_in != 0, cfd_among<3, 2>(cfd_act_pieces()));
     }
     CFD_LAUNCH_CHECK("cfd_fno_head_bwd");
     const HeadTail ht = cfd_int_head_tail(part, gw1, gb1, gw2, gb2, nullptr, B, C, Co, HW, 0.f);  // (the loss rows belong to the one-pass kernel)
@@ -1704,41 +1673,14 @@ int cfd_int_fno_head_train_f(const void* a, const float* mask, const float* labe
     // "head_waves" = 4 / 8 forces either form
     const int hw = cfd_tune_get(CFD_TUNE_HEAD_WAVES);
     const bool w8 = dt == CFD_DT_F32 && (hw == 8 || (hw != 4 && C > 20));
-#define CFD_HT_P(K_, V_, A_, T_, P_)                                                                                      \
-    do {                                                                                                                  \
-        if constexpr (sizeof(T_) == 4) {                                                                                  \
-            if (w8) {                                                                                                     \
-                hipLaunchKernelGGL((k_head_bwd<K_, V_, A_, true, T_, P_, 8>), dim3(blocks), dim3(512), 0, st, (const T_*)a, mask, label, (const float*)nullptr, \
-                                   (const float*)nullptr, coef, w1, b1, w2, ga, part, B, C, Co, HW, preds, b2, c0v, c1v); \
-                break;                                                                                                    \
-            }                                                                                                             \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((k_head_bwd<K_, V_, A_, true, T_, P_>), dim3(blocks), dim3(256), 0, st, (const T_*)a, mask, label, (const float*)nullptr, \
-                           (const float*)nullptr, coef, w1, b1, w2, ga, part, B, C, Co, HW, preds, b2, c0v, c1v);         \
-    } while (0)
-#define CFD_HT(K_, V_, A_, T_)                                                                        \
-    do {                                                                                              \
-        if constexpr (sizeof(T_) == 4) { if (ap3) CFD_HT_P(K_, V_, A_, T_, 3); else CFD_HT_P(K_, V_, A_, T_, 2); } \
-        else CFD_HT_P(K_, V_, A_, T_, 2);                                                             \
-    } while (0)
-#define CFD_HT_VA(K_)                                                     \
-    do {                                                                  \
-        if (dt == CFD_DT_BF16) {                                          \
-            if (v4 && act_in) CFD_HT(K_, true, true, __bf16);             \
-            else if (v4) CFD_HT(K_, true, false, __bf16);                 \
-            else if (act_in) CFD_HT(K_, false, true, __bf16);             \
-            else CFD_HT(K_, false, false, __bf16);                        \
-        } else if (v4 && act_in) CFD_HT(K_, true, true, float);           \
-        else if (v4) CFD_HT(K_, true, false, float);                      \
-        else if (act_in) CFD_HT(K_, false, true, float);                  \
-        else CFD_HT(K_, false, false, float);                             \
-    } while (0)
-    if (C <= 8) CFD_HT_VA(2);
-    else if (C <= 20) CFD_HT_VA(5);
-    else CFD_HT_VA(8);
-#undef CFD_HT_VA
-#undef CFD_HT
-#undef CFD_HT_P
+    cfd_dispatch([&](auto K, auto T, auto V, auto A, auto P, auto NWV) {
+        using TA = CFD_T(T);
+        if constexpr (sizeof(TA) == 4 || (CFD_I(P) == 2 && CFD_I(NWV) == 4))
+            hipLaunchKernelGGL((k_head_bwd<CFD_I(K), CFD_B(V), CFD_B(A), true, TA, CFD_I(P), CFD_I(NWV)>), dim3(blocks), dim3(64 * CFD_I(NWV)), 0, st,
+                               (const TA*)a, mask, label, (const float*)nullptr, (const float*)nullptr, coef, w1, b1, w2, ga, part, B, C, Co, HW,
+                               preds, b2, c0v, c1v);
+    }, head_cq(C), cfd_storage(dt), v4, act_in != 0, cfd_among<3, 2>(ap3 ? 3 : 2),
+       cfd_among<8, 4>(w8 ? 8 : 4));
     }
     CFD_LAUNCH_CHECK("cfd_fno_head_train");
     const HeadTail ht = cfd_int_head_tail(part, gw1, gb1, gw2, gb2, sums, B, C, Co, HW, count);
@@ -1760,18 +1702,10 @@ static int head_fwd_co(const float* a, const float* mask, const float* label, co
     float* part = label ? (float*)ws : nullptr;
     {
     CFD_PROF_W("k_head_fwd_co", st, B * HW * (4.0 * C + 4.0 * (1 + (label ? 2 : 1) * Co)), 2.0 * B * HW * (double)HEAD_HD * (C + Co));
-#define CFD_HFC(Q_, A_, N_) \
-    hipLaunchKernelGGL((k_head_fwd_co<Q_, A_, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW)
-#define CFD_HFC_Q(Q_)                                                                  \
-    do {                                                                               \
-        if (Co <= 4) { if (act_in) CFD_HFC(Q_, true, 4); else CFD_HFC(Q_, false, 4); } \
-        else { if (act_in) CFD_HFC(Q_, true, 8); else CFD_HFC(Q_, false, 8); }         \
-    } while (0)
-    if (C <= 8) CFD_HFC_Q(2);
-    else if (C <= 20) CFD_HFC_Q(5);
-    else CFD_HFC_Q(8);
-#undef CFD_HFC_Q
-#undef CFD_HFC
+    cfd_dispatch([&](auto Q, auto A, auto N) {
+        hipLaunchKernelGGL((k_head_fwd_co<CFD_I(Q), CFD_B(A), CFD_I(N)>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part,
+                           B, C, Co, HW);
+    }, head_cq(C), act_in != 0, cfd_among<4, 8>(Co <= 4 ? 4 : 8));
     }
     CFD_LAUNCH_CHECK("cfd_fno_head_fwd(channels)");
     if (label) {
@@ -1791,19 +1725,10 @@ static int head_bwd_co(const float* a, const float* mask, const float* label, co
     float* part = (float*)ws;
     {
     CFD_PROF_W("k_head_bwd_co", st, 4.0 * B * HW * (2.0 * C + 1 + 2.0 * Co), 2.0 * B * HW * (double)HEAD_HD * (3.0 * C + 2.0 * Co));
-#define CFD_HBC(K_, A_, N_)                                                                                                            \
-    hipLaunchKernelGGL((k_head_bwd_co<K_, A_, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, preds, gext, coef, w1, b1, w2, ga, part, B, \
-                       C, Co, HW)
-#define CFD_HBC_K(K_)                                                                  \
-    do {                                                                               \
-        if (Co <= 4) { if (act_in) CFD_HBC(K_, true, 4); else CFD_HBC(K_, false, 4); } \
-        else { if (act_in) CFD_HBC(K_, true, 8); else CFD_HBC(K_, false, 8); }         \
-    } while (0)
-    if (C <= 8) CFD_HBC_K(2);
-    else if (C <= 20) CFD_HBC_K(5);
-    else CFD_HBC_K(8);
-#undef CFD_HBC_K
-#undef CFD_HBC
+    cfd_dispatch([&](auto K, auto A, auto N) {
+        hipLaunchKernelGGL((k_head_bwd_co<CFD_I(K), CFD_B(A), CFD_I(N)>), dim3(blocks), dim3(256), 0, st, a, mask, label, preds, gext, coef, w1, b1,
+                           w2, ga, part, B, C, Co, HW);
+    }, head_cq(C), act_in != 0, cfd_among<4, 8>(Co <= 4 ? 4 : 8));
     }
     CFD_LAUNCH_CHECK("cfd_fno_head_bwd(channels)");
     const HeadTail ht = cfd_int_head_tail(part, gw1, gb1, gw2, gb2, nullptr, B, C, Co, HW, 0.f);

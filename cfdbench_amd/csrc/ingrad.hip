@@ -13,6 +13,7 @@
 // part[(b * S + s) * P + k]; k_ingrad_cp adds the S records of an entry in order s = 0 .. S - 1.  With S == 1 the workgroup writes
 // d_case_params itself and no record exists.  No atomics: the result depends on the shape, S and VEC alone.
 #include "cfd_common.h"
+#include "cfd_launch.h"
 
 namespace {
 
@@ -181,18 +182,10 @@ int cfd_int_fno_ingrad(const float* g0, const float* w, float* d_inputs, float* 
     {
         CFD_PROF_W("k_ingrad", st, 4.0 * B * HW * ((double)C + (d_inputs ? in_chan : 0)),
                    2.0 * B * HW * (double)C * ((d_inputs ? in_chan : 0) + (d_case_params ? P : 0)));
-#define CFD_IG(V_, N_, CP_) \
-    hipLaunchKernelGGL((k_ingrad<V_, N_, CP_>), grid, dim3(256), 0, st, g0, w, d_inputs, d_case_params, part, in_chan, P, C, HW)
-#define CFD_IG_N(V_)                                                             \
-    do {                                                                         \
-        if (d_case_params) { if (in_chan <= 4) CFD_IG(V_, 4, true); else CFD_IG(V_, 8, true); } \
-        else { if (in_chan <= 4) CFD_IG(V_, 4, false); else CFD_IG(V_, 8, false); }             \
-    } while (0)
-        if (vec == 4) CFD_IG_N(4);
-        else if (vec == 2) CFD_IG_N(2);
-        else CFD_IG_N(1);
-#undef CFD_IG_N
-#undef CFD_IG
+        cfd_dispatch([&](auto V, auto N, auto CP) {
+            hipLaunchKernelGGL((k_ingrad<CFD_I(V), CFD_I(N), CFD_B(CP)>), grid, dim3(256), 0, st, g0, w, d_inputs, d_case_params, part, in_chan, P,
+                               C, HW);
+        }, cfd_among<4, 2, 1>(vec), cfd_among<4, 8>(in_chan <= 4 ? 4 : 8), d_case_params != nullptr);
         CFD_LAUNCH_CHECK("cfd_fno_ingrad");
     }
     if (part) {

@@ -16,6 +16,7 @@
 // the entries are processed in stages of 16 (one MFMA row tile) as they land.  The weight-gradient partial sums of a chunk leave
 // through LDS in the layout k_spec_wgrad_reduce / cfd_tail.h already read: part[chunk][i][o][mode] complex.
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"
 
 #ifndef CFD_MM_EXP
@@ -300,11 +301,7 @@ static int mm_launch(const float* xin, const float* xw, const float* w1, const f
     const int ntile = M / CFD_MM_T, npair = (ntile + 1) / 2;
     const unsigned grid = (unsigned)((npair * nchunk + 7) / 8) * 16u;
     const size_t lds = cfd_mm_lds_bytes<C>(WGRAD, RMAX);
-    static bool attr_set = false;  // > 64 KB of dynamic LDS needs the attribute once per kernel
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_modes_mfma<C, CONJT, WGRAD, NST, RMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+    CFD_TRY((cfd_allow_lds<k_modes_mfma<C, CONJT, WGRAD, NST, RMAX>>(lds, "cfd_spectral_mix(mfma)")));
     hipLaunchKernelGGL((k_modes_mfma<C, CONJT, WGRAD, NST, RMAX>), dim3(grid), dim3(512), lds, st, xin, xw, w1, w2, z, part, B, BC, M, half,
                        ntile, npair, nchunk);
     return CFD_OK;
@@ -314,17 +311,18 @@ static int mm_launch(const float* xin, const float* xw, const float* w1, const f
 int cfd_int_modes_mix(const cfd_plan* p, const float* xin, const float* w1, const float* w2, float* z, int B, int C, int conj_t,
                       void* stream) {
     const int M = 2 * p->m1 * p->m2, half = p->m1 * p->m2;
-    int BC, nchunk;
+    int BC, nchunk, rc;
     hipStream_t st = (hipStream_t)stream;
     if (C == 32) {
         cfd_mm_geometry(B, M / CFD_MM_T, 37, true, &BC, &nchunk);
-        if (conj_t) mm_launch<32, true, false, 3, 37>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
-        else mm_launch<32, false, false, 3, 37>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
+        if (conj_t) rc = mm_launch<32, true, false, 3, 37>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
+        else rc = mm_launch<32, false, false, 3, 37>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
     } else {
         cfd_mm_geometry(B, M / CFD_MM_T, 32, false, &BC, &nchunk);
-        if (conj_t) mm_launch<20, true, false, 2, 32>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
-        else mm_launch<20, false, false, 2, 32>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
+        if (conj_t) rc = mm_launch<20, true, false, 2, 32>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
+        else rc = mm_launch<20, false, false, 2, 32>(xin, nullptr, w1, w2, z, nullptr, B, BC, nchunk, M, half, st);
     }
+    CFD_TRY(rc);
     CFD_LAUNCH_CHECK("cfd_spectral_mix(mfma)");
     return CFD_OK;
 }
@@ -336,7 +334,7 @@ int cfd_int_modes_mixadj_wgrad(const cfd_plan* p, const float* xh, const float* 
     int BC, nchunk;
     cfd_mm_geometry(B, M / CFD_MM_T, 40, true, &BC, &nchunk);
     (void)C;
-    mm_launch<20, true, true, 3, 40>(gh, xh, w1, w2, gz, part, B, BC, nchunk, M, half, (hipStream_t)stream);
+    CFD_TRY((mm_launch<20, true, true, 3, 40>(gh, xh, w1, w2, gz, part, B, BC, nchunk, M, half, (hipStream_t)stream)));
     CFD_LAUNCH_CHECK("cfd_spectral_mix_adj_wgrad(mfma)");
     *nchunk_out = nchunk;
     return CFD_OK;

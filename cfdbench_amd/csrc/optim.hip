@@ -3,9 +3,9 @@
 // One walk over the flat buffer (flat_walk), one block that finishes a row of fc0's gradient (stem_row); what happens to an element is an
 // operation struct: AdamOp, AccumOp, SumSqOp.
 #include <initializer_list>
-#include <type_traits>
 
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"
 
 // ------------------------------------------------------------------------------------------------------
@@ -330,15 +330,6 @@ static int checked_job(const StemAdamJob* job, StemAdamJob& jb) {
     CFD_REQUIRE(!jb.part || (jb.P <= 8 && jb.in_chan + 3 + jb.P < 256), CFD_ERR_UNSUPPORTED, "cfd_fno_adam_step: lifting layer with %d case parameters", jb.P);
     return CFD_OK;
 }
-// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): run-time flags to template arguments, one instantiation per combination
-template <typename F>
-static void with_bools(F&& f) { f(); }
-template <typename F, typename... Rest>
-static void with_bools(F&& f, bool b, Rest... rest) {
-    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
-#define CFD_B(c) decltype(c)::value
 
 int cfd_int_adam_flat_f(float* param, float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, int step, float grad_scale, const float* sums, const StemAdamJob* job, float* clip,

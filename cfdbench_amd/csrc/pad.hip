@@ -7,6 +7,7 @@
 // are multiples of 4 and every pointer is 16-byte aligned (then a group of four columns is interior or band as a whole), 4-byte accesses
 // otherwise.  The band is WRITTEN on every call: the workspace is the caller's and may hold anything.
 #include "cfd_common.h"
+#include "cfd_launch.h"
 
 namespace {
 
@@ -176,12 +177,10 @@ int cfd_int_stem_pad(const float* inputs, const float* mask, const float* case_p
     const int Hp = H + pad, Wp = W + pad;
     const double rx = 1.0 / (double)(H - 1), ry = 1.0 / (double)(W - 1);
     CFD_PROF_W("k_stem_pad", st, (double)B * (4.0 * H * W * (in_chan + 1) + 4.0 * C * Hp * Wp), 2.0 * B * H * W * (double)C * (in_chan + 3 + P));
-    if (pad_vec4(W, pad, (uintptr_t)inputs | (uintptr_t)mask | (uintptr_t)out))
-        hipLaunchKernelGGL(k_stem_pad<4>, plane_grid(B, Hp * (Wp / 4)), dim3(256), 0, st, inputs, mask, case_params, w, bias, out, coords, B,
-                           in_chan, P, C, H, W, pad, rx, ry, cfd_div_make((unsigned)(Wp / 4)));
-    else
-        hipLaunchKernelGGL(k_stem_pad<1>, plane_grid(B, Hp * Wp), dim3(256), 0, st, inputs, mask, case_params, w, bias, out, coords, B, in_chan,
-                           P, C, H, W, pad, rx, ry, cfd_div_make((unsigned)Wp));
+    cfd_dispatch([&](auto V) {  // (V pixels of a padded row per thread)
+        hipLaunchKernelGGL(k_stem_pad<CFD_I(V)>, plane_grid(B, Hp * (Wp / CFD_I(V))), dim3(256), 0, st, inputs, mask, case_params, w, bias, out,
+                           coords, B, in_chan, P, C, H, W, pad, rx, ry, cfd_div_make((unsigned)(Wp / CFD_I(V))));
+    }, cfd_among<4, 1>(pad_vec4(W, pad, (uintptr_t)inputs | (uintptr_t)mask | (uintptr_t)out) ? 4 : 1));
     CFD_LAUNCH_CHECK("cfd_fno_stem_pad");
     return CFD_OK;
 }
@@ -191,10 +190,10 @@ int cfd_int_pad_crop(const float* in, float* out, long n, int H, int W, int pad,
     CFD_PAD_REQUIRE("cfd_fno_pad_crop");
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W("k_pad_crop", st, 8.0 * n * H * W, 0.0);
-    if (pad_vec4(W, pad, (uintptr_t)in | (uintptr_t)out))
-        hipLaunchKernelGGL(k_pad_crop<4>, plane_grid(n, H * (W / 4)), dim3(256), 0, st, in, out, n, H, W, pad, cfd_div_make((unsigned)(W / 4)));
-    else
-        hipLaunchKernelGGL(k_pad_crop<1>, plane_grid(n, H * W), dim3(256), 0, st, in, out, n, H, W, pad, cfd_div_make((unsigned)W));
+    cfd_dispatch([&](auto V) {
+        hipLaunchKernelGGL(k_pad_crop<CFD_I(V)>, plane_grid(n, H * (W / CFD_I(V))), dim3(256), 0, st, in, out, n, H, W, pad,
+                           cfd_div_make((unsigned)(W / CFD_I(V))));
+    }, cfd_among<4, 1>(pad_vec4(W, pad, (uintptr_t)in | (uintptr_t)out) ? 4 : 1));
     CFD_LAUNCH_CHECK("cfd_fno_pad_crop");
     return CFD_OK;
 }
@@ -205,11 +204,10 @@ int cfd_int_pad_embed(const float* in, float* out, long n, int H, int W, int pad
     hipStream_t st = (hipStream_t)stream;
     const int Hp = H + pad, Wp = W + pad;
     CFD_PROF_W("k_pad_embed", st, 4.0 * n * ((double)H * W + (double)Hp * Wp), 0.0);
-    if (pad_vec4(W, pad, (uintptr_t)in | (uintptr_t)out))
-        hipLaunchKernelGGL(k_pad_embed<4>, plane_grid(n, Hp * (Wp / 4)), dim3(256), 0, st, in, out, n, H, W, pad,
-                           cfd_div_make((unsigned)(Wp / 4)));
-    else
-        hipLaunchKernelGGL(k_pad_embed<1>, plane_grid(n, Hp * Wp), dim3(256), 0, st, in, out, n, H, W, pad, cfd_div_make((unsigned)Wp));
+    cfd_dispatch([&](auto V) {
+        hipLaunchKernelGGL(k_pad_embed<CFD_I(V)>, plane_grid(n, Hp * (Wp / CFD_I(V))), dim3(256), 0, st, in, out, n, H, W, pad,
+                           cfd_div_make((unsigned)(Wp / CFD_I(V))));
+    }, cfd_among<4, 1>(pad_vec4(W, pad, (uintptr_t)in | (uintptr_t)out) ? 4 : 1));
     CFD_LAUNCH_CHECK("cfd_fno_pad_embed");
     return CFD_OK;
 }

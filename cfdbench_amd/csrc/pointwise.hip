@@ -3,6 +3,7 @@
 //   feature assembly + fc0    src/models/fno/fno2d.py:189-217      -> k_stem_fwd / k_chan_wgrad<STEM>
 //   MseLoss                   src/models/loss.py:22-37             -> k_loss_part / k_loss_final
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"
 
 // ------------------------------------------------------------------------------------------------------
@@ -195,6 +196,9 @@ __global__ __launch_bounds__(256) void k_stem_fwd4(const float* __restrict__ inp
     }
 }
 
+// channels a thread (or tile) is compiled for: the next multiple of 8
+static cfd_among_t<8, 16, 24, 32> chan_bucket(int C) { return {C <= 8 ? 8 : C <= 16 ? 16 : C <= 24 ? 24 : 32}; }
+
 extern "C" int cfd_fno_stem_fwd(const cfd_plan* p, const float* inputs, const float* mask, const float* case_params,
                                 const float* w, const float* bias, float* out, int B, int in_chan, int P, int C,
                                 void* stream) {
@@ -217,34 +221,21 @@ int cfd_int_fno_stem_fwd(const cfd_plan* p, const float* inputs, const float* ma
     hipStream_t st = (hipStream_t)stream;
     CFD_PROF_W("k_stem_fwd", st, B * p->H * p->W * (4.0 * (in_chan + 1) + (double)cfd_dt_size(dt) * C),
                2.0 * B * p->H * p->W * (double)C * (in_chan + 3 + P));
-#define CFD_STEM(CPV)                                                                                              \
-    do {                                                                                                           \
-        if (dt == CFD_DT_BF16)                                                                                     \
-            hipLaunchKernelGGL((k_stem_fwd<CPV, __bf16>), dim3(blocks), dim3(256), 0, st, inputs, mask, case_params, \
-                               (const float*)p->d_gx, (const float*)p->d_gy, w, bias, (__bf16*)out_, B, in_chan, P, C, p->H, p->W); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((k_stem_fwd<CPV, float>), dim3(blocks), dim3(256), 0, st, inputs, mask, case_params, \
-                               (const float*)p->d_gx, (const float*)p->d_gy, w, bias, out, B, in_chan, P, C, p->H, p->W); \
-    } while (0)
     const bool v4 = dt == CFD_DT_F32 && p->W % 4 == 0 && (((uintptr_t)inputs | (uintptr_t)mask | (uintptr_t)out | (uintptr_t)p->d_gy) % 16) == 0;
     if (v4) {
         const long quads = total / 4;
         int blocks4 = (int)((quads + 255) / 256);
         if (blocks4 > 2048) blocks4 = 2048;
-#define CFD_STEM4(CPV)                                                                                             \
-    hipLaunchKernelGGL((k_stem_fwd4<CPV>), dim3(blocks4), dim3(256), 0, st, inputs, mask, case_params,             \
-                       (const float*)p->d_gx, (const float*)p->d_gy, w, bias, out, B, in_chan, P, C, p->H, p->W)
-        if (C <= 8) CFD_STEM4(8);
-        else if (C <= 16) CFD_STEM4(16);
-        else if (C <= 24) CFD_STEM4(24);
-        else CFD_STEM4(32);
-#undef CFD_STEM4
+        cfd_dispatch([&](auto CPV) {
+            hipLaunchKernelGGL((k_stem_fwd4<CFD_I(CPV)>), dim3(blocks4), dim3(256), 0, st, inputs, mask, case_params, (const float*)p->d_gx,
+                               (const float*)p->d_gy, w, bias, out, B, in_chan, P, C, p->H, p->W);
+        }, chan_bucket(C));
+    } else {
+        cfd_dispatch([&](auto CPV, auto T) {
+            hipLaunchKernelGGL((k_stem_fwd<CFD_I(CPV), CFD_T(T)>), dim3(blocks), dim3(256), 0, st, inputs, mask, case_params, (const float*)p->d_gx,
+                               (const float*)p->d_gy, w, bias, (CFD_T(T)*)out_, B, in_chan, P, C, p->H, p->W);
+        }, chan_bucket(C), cfd_storage(dt));
     }
-    else if (C <= 8) CFD_STEM(8);
-    else if (C <= 16) CFD_STEM(16);
-    else if (C <= 24) CFD_STEM(24);
-    else CFD_STEM(32);
-#undef CFD_STEM
     CFD_LAUNCH_CHECK("cfd_fno_stem_fwd");
     return CFD_OK;
 }
@@ -505,24 +496,11 @@ static int launch_chanmix_b3(const TA* in, const float* w, const float* bias, fl
     CFD_PROF_W(transpose ? "k_chanmix_t" : (act ? "k_chanmix_act" : "k_chanmix"), st, B * HW * ((double)ea * Ci + 4.0 * Co),
                2.0 * B * HW * (double)Ci * Co);
     const bool ap3 = sizeof(TA) == 4 && cfd_act_pieces() == 3;  // bf16 storage keeps two pieces
-#define CFD_CB3_P(M_, V_, A_, P_) \
-    hipLaunchKernelGGL((k_chanmix_b3<M_, V_, A_, TA, P_>), dim3(blocks), dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose)
-#define CFD_CB3(M_, V_, A_)                                                                   \
-    do {                                                                                      \
-        if constexpr (sizeof(TA) == 4) { if (ap3) CFD_CB3_P(M_, V_, A_, 3); else CFD_CB3_P(M_, V_, A_, 2); } \
-        else CFD_CB3_P(M_, V_, A_, 2);                                                        \
-    } while (0)
-#define CFD_CB3_V(M_)                                                      \
-    do {                                                                   \
-        if (vec == 4) { if (act) CFD_CB3(M_, 4, true); else CFD_CB3(M_, 4, false); } \
-        else if (vec == 2) { if (act) CFD_CB3(M_, 2, true); else CFD_CB3(M_, 2, false); } \
-        else { if (act) CFD_CB3(M_, 1, true); else CFD_CB3(M_, 1, false); }  \
-    } while (0)
-    if (Co <= 16) CFD_CB3_V(1);
-    else CFD_CB3_V(2);
-#undef CFD_CB3_V
-#undef CFD_CB3
-#undef CFD_CB3_P
+    cfd_dispatch([&](auto M, auto V, auto A, auto P) {
+        if constexpr (sizeof(TA) == 4 || CFD_I(P) == 2)
+            hipLaunchKernelGGL((k_chanmix_b3<CFD_I(M), CFD_I(V), CFD_B(A), TA, CFD_I(P)>), dim3(blocks), dim3(256), 0, st, in, w, bias, out, B, Ci, Co,
+                               HW, transpose);
+    }, cfd_among<1, 2>(Co <= 16 ? 1 : 2), cfd_among<4, 2, 1>(vec), act != 0, cfd_among<3, 2>(ap3 ? 3 : 2));
     CFD_LAUNCH_CHECK("cfd_chanmix");
     return CFD_OK;
 }
@@ -535,10 +513,9 @@ static int launch_chanmix(const float* in, const float* w, const float* bias, fl
     if (blocks > 4096) blocks = 4096;
     CFD_PROF_W(transpose ? "k_chanmix_t" : (act ? "k_chanmix_act" : "k_chanmix"), st, 4.0 * B * HW * ((double)Ci + Co),
                2.0 * B * HW * (double)Ci * Co);
-    if (act)
-        hipLaunchKernelGGL((k_chanmix<CPO, VEC, true>), dim3(blocks), dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose);
-    else
-        hipLaunchKernelGGL((k_chanmix<CPO, VEC, false>), dim3(blocks), dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose);
+    with_bools([&](auto A) {
+        hipLaunchKernelGGL((k_chanmix<CPO, VEC, CFD_B(A)>), dim3(blocks), dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose);
+    }, act != 0);
     CFD_LAUNCH_CHECK("cfd_chanmix");
     return CFD_OK;
 }
@@ -556,20 +533,10 @@ int cfd_int_chanmix(const void* in, const float* w, const float* bias, void* out
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     CFD_PROF_W(act_in ? "k_chanmix_act" : "k_chanmix", st, B * HW * (2.0 * Ci + 4.0 * Co), 2.0 * B * HW * (double)Ci * Co);
-#define CFD_CMB(CPV, VW, A_)                                                                                                  \
-    hipLaunchKernelGGL((k_chanmix<CPV, VW, A_, __bf16, float>), dim3(blocks), dim3(256), 0, st, (const __bf16*)in, w, bias, (float*)out, B, \
-                       Ci, Co, HW, transpose)
-#define CFD_CMB_VA(CPV)                                                    \
-    do {                                                                   \
-        if (VEC == 2) { if (act_in) CFD_CMB(CPV, 2, true); else CFD_CMB(CPV, 2, false); } \
-        else { if (act_in) CFD_CMB(CPV, 1, true); else CFD_CMB(CPV, 1, false); }          \
-    } while (0)
-    if (Co <= 8) CFD_CMB_VA(8);
-    else if (Co <= 16) CFD_CMB_VA(16);
-    else if (Co <= 24) CFD_CMB_VA(24);
-    else CFD_CMB_VA(32);
-#undef CFD_CMB_VA
-#undef CFD_CMB
+    cfd_dispatch([&](auto CPV, auto VW, auto A) {
+        hipLaunchKernelGGL((k_chanmix<CFD_I(CPV), CFD_I(VW), CFD_B(A), __bf16, float>), dim3(blocks), dim3(256), 0, st, (const __bf16*)in, w, bias,
+                           (float*)out, B, Ci, Co, HW, transpose);
+    }, chan_bucket(Co), cfd_among<2, 1>(VEC), act_in != 0);
     CFD_LAUNCH_CHECK("cfd_chanmix(bf16 storage)");
     return CFD_OK;
 }
@@ -588,15 +555,13 @@ extern "C" int cfd_chanmix(const float* in, const float* w, const float* bias, f
     // pixels per thread: 4 (16-B accesses) while the accumulator tile stays small, 2 (8-B) for wide outputs
     const bool v4 = HW % 4 == 0 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0;
     const bool v2 = HW % 2 == 0 && ((uintptr_t)in % 8) == 0 && ((uintptr_t)out % 8) == 0;
-#define CFD_CM(CPV, VW)                                                                               \
-    return (VW == 4 && v4) ? launch_chanmix<CPV, VW>(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, st) \
-           : v2            ? launch_chanmix<CPV, 2>(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, st)  \
-                           : launch_chanmix<CPV, 1>(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, st)
-    if (Co <= 8) CFD_CM(8, 4);
-    if (Co <= 16) CFD_CM(16, 4);
-    if (Co <= 24) CFD_CM(24, 2);
-    CFD_CM(32, 2);
-#undef CFD_CM
+    const int vw = (v4 && Co <= 16) ? 4 : v2 ? 2 : 1;  // (25 .. 32 output channels: at most two pixels)
+    int rc = CFD_OK;
+    cfd_dispatch([&](auto CPV, auto VW) {
+        if constexpr (CFD_I(VW) != 4 || CFD_I(CPV) <= 16)
+            rc = launch_chanmix<CFD_I(CPV), CFD_I(VW)>(in, w, bias, out, B, Ci, Co, HW, act_in, transpose, st);
+    }, chan_bucket(Co), cfd_among<4, 2, 1>(vw));
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1050,62 +1015,34 @@ static int launch_wgrad(const float* g, const TIN* in, StemSrc ss, float* gw, fl
                                                                                             : 1;
     float* part = (float*)ws;
     const bool ap3 = sizeof(TIN) == 4 && cfd_act_pieces() == 3;  // bf16 storage keeps two pieces
-#define CFD_WG_P(M_, N_, V_, A_, P_)                                                                             \
-    hipLaunchKernelGGL((k_chan_wgrad<M_, N_, V_, A_, STEM, TIN, P_>), dim3(blocks), dim3(256), 0, st, g, in, ss, part, B, \
-                       Ci, Co, HW)
-#define CFD_WG(M_, N_, V_, A_)                                                                \
-    do {                                                                                      \
-        if constexpr (sizeof(TIN) == 4) { if (ap3) CFD_WG_P(M_, N_, V_, A_, 3); else CFD_WG_P(M_, N_, V_, A_, 2); } \
-        else CFD_WG_P(M_, N_, V_, A_, 2);                                                     \
-    } while (0)
-#define CFD_WG_VA(M_, N_)                                                                     \
-    do {                                                                                      \
-        if (vec == 4) { if (act) CFD_WG(M_, N_, 4, true); else CFD_WG(M_, N_, 4, false); }    \
-        else if (vec == 2) { if constexpr (sizeof(TIN) == 4) { if (act) CFD_WG(M_, N_, 2, true); else CFD_WG(M_, N_, 2, false); } } \
-        else { if (act) CFD_WG(M_, N_, 1, true); else CFD_WG(M_, N_, 1, false); }             \
-    } while (0)
     // 17 .. 24 channels on both sides: the second tiles once per group of 4 (up to 20 channels) or 2 chunks (k_chan_wgrad_grp);
     // chan_wgrad_grp = 0 keeps these shapes on the per-chunk kernel.  The stem's generated columns sit in the tile: per chunk.
     // (HW < 2^24: the kernel adds a 32-bit lane offset of up to 16 planes to a scalar chunk address.)
     const int grp = (STEM || MT != 2 || NT != 2 || Ci < 17 || Co < 17 || Ci > 24 || Co > 24 || HW >= (1 << 24) || cfd_tune_get(CFD_TUNE_CHAN_WGRAD_GRP) == 0) ? 0
                     : (Ci <= 20 && Co <= 20)                                                                                              ? 4
                                                                                                                                           : 2;
-#define CFD_WGG_P(G_, V_, A_, P_) \
-    hipLaunchKernelGGL((k_chan_wgrad_grp<G_, V_, A_, TIN, P_>), dim3(blocks), dim3(256), 0, st, g, in, part, B, Ci, Co, HW)
-#define CFD_WGG(G_, V_, A_)                                                                \
-    do {                                                                                   \
-        if constexpr (sizeof(TIN) == 4) { if (ap3) CFD_WGG_P(G_, V_, A_, 3); else CFD_WGG_P(G_, V_, A_, 2); } \
-        else CFD_WGG_P(G_, V_, A_, 2);                                                     \
-    } while (0)
-#define CFD_WGG_VA(G_)                                                                     \
-    do {                                                                                   \
-        if (vec == 4) { if (act) CFD_WGG(G_, 4, true); else CFD_WGG(G_, 4, false); }       \
-        else if (vec == 2) { if constexpr (sizeof(TIN) == 4) { if (act) CFD_WGG(G_, 2, true); else CFD_WGG(G_, 2, false); } } \
-        else { if (act) CFD_WGG(G_, 1, true); else CFD_WGG(G_, 1, false); }                \
-    } while (0)
+    if (!grp && (MT > 2 || NT > 3)) {
+        cfd_set_error("cfd_chan_wgrad: Co=%d Ci=%d unsupported tile shape", Co, Ci);
+        return CFD_ERR_UNSUPPORTED;
+    }
     {
     // stem: the gradient tensor + the raw input channels (features are generated); otherwise gradient + activation
     CFD_PROF_W(STEM ? "k_chan_wgrad_stem" : grp ? "k_chan_wgrad_grp" : "k_chan_wgrad", st, (double)B * HW * (4.0 * Co + sizeof(TIN) * (STEM ? 3 : Ci)),
                2.0 * B * HW * (double)Co * (Ci + 1));
-    if (grp == 4) { if constexpr (!STEM) CFD_WGG_VA(4); }
-    else if (grp == 2) { if constexpr (!STEM) CFD_WGG_VA(2); }
-    else if (MT == 1 && NT == 1) CFD_WG_VA(1, 1);
-    else if (MT == 1 && NT == 2) CFD_WG_VA(1, 2);
-    else if (MT == 2 && NT == 1) CFD_WG_VA(2, 1);
-    else if (MT == 2 && NT == 2) CFD_WG_VA(2, 2);
-    else if (MT == 2 && NT == 3) CFD_WG_VA(2, 3);
-    else if (MT == 1 && NT == 3) CFD_WG_VA(1, 3);
-    else {
-        cfd_set_error("cfd_chan_wgrad: Co=%d Ci=%d unsupported tile shape", Co, Ci);
-        return CFD_ERR_UNSUPPORTED;
+    // (bf16 `in` has no 2-element form and keeps two pieces)
+    if (grp)
+        cfd_dispatch([&](auto G, auto V, auto A, auto P) {
+            if constexpr (!STEM && (sizeof(TIN) == 4 || (CFD_I(V) != 2 && CFD_I(P) == 2)))
+                hipLaunchKernelGGL((k_chan_wgrad_grp<CFD_I(G), CFD_I(V), CFD_B(A), TIN, CFD_I(P)>), dim3(blocks), dim3(256), 0, st, g, in, part, B, Ci,
+                                   Co, HW);
+        }, cfd_among<4, 2>(grp), cfd_among<4, 2, 1>(vec), act != 0, cfd_among<3, 2>(ap3 ? 3 : 2));
+    else
+        cfd_dispatch([&](auto M, auto N, auto V, auto A, auto P) {
+            if constexpr (sizeof(TIN) == 4 || (CFD_I(V) != 2 && CFD_I(P) == 2))
+                hipLaunchKernelGGL((k_chan_wgrad<CFD_I(M), CFD_I(N), CFD_I(V), CFD_B(A), STEM, TIN, CFD_I(P)>), dim3(blocks), dim3(256), 0, st, g, in,
+                                   ss, part, B, Ci, Co, HW);
+        }, cfd_among<1, 2>(MT), cfd_among<1, 2, 3>(NT), cfd_among<4, 2, 1>(vec), act != 0, cfd_among<3, 2>(ap3 ? 3 : 2));
     }
-    }
-#undef CFD_WGG_VA
-#undef CFD_WGG
-#undef CFD_WGG_P
-#undef CFD_WG_VA
-#undef CFD_WG
-#undef CFD_WG_P
     CFD_LAUNCH_CHECK("cfd_chan_wgrad");
     if (defer) {
         *defer = ChanWgradTail{(const float*)part, gw, gb, blocks, Co, Ci};
@@ -1582,12 +1519,10 @@ extern "C" int cfd_label_energy_coef(const float* label, const float* mask, floa
     long want = ((long)units + 1023) / 1024;  // four units per thread
     const int blocks = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
     CFD_PROF_W("k_label_energy", st, 4.0 * B * HW * (Co + 1.0), 2.0 * B * Co * HW);
-    if (v4)
-        hipLaunchKernelGGL((k_label_energy_part<4>), dim3(blocks), dim3(256), 0, st, label, mask, (float*)ws, units, (unsigned)HW,
-                           cfd_div_make((unsigned)HW / 4), cfd_div_make((unsigned)Co));
-    else
-        hipLaunchKernelGGL((k_label_energy_part<1>), dim3(blocks), dim3(256), 0, st, label, mask, (float*)ws, units, (unsigned)HW,
-                           cfd_div_make((unsigned)HW), cfd_div_make((unsigned)Co));
+    cfd_dispatch([&](auto V) {
+        hipLaunchKernelGGL((k_label_energy_part<CFD_I(V)>), dim3(blocks), dim3(256), 0, st, label, mask, (float*)ws, units, (unsigned)HW,
+                           cfd_div_make((unsigned)HW / CFD_I(V)), cfd_div_make((unsigned)Co));
+    }, cfd_among<4, 1>((int)vec));
     CFD_LAUNCH_CHECK("cfd_label_energy_coef(part)");
     hipLaunchKernelGGL(k_label_energy_coef, dim3(1), dim3(64), 0, st, (const float*)ws, blocks, (float)((double)B * Co * HW), sums,
                        coef, which, upstream);
@@ -1664,8 +1599,9 @@ static int launch_dropout_gelu(const float* x, const float* gy, float* out, size
     if (n == 0) return CFD_OK;
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (bwd) hipLaunchKernelGGL((k_dropout_gelu<true>), dim3((unsigned)blocks), dim3(256), 0, st, x, gy, out, n / 4, p, seed, step);
-    else hipLaunchKernelGGL((k_dropout_gelu<false>), dim3((unsigned)blocks), dim3(256), 0, st, x, gy, out, n / 4, p, seed, step);
+    with_bools([&](auto BWD) {
+        hipLaunchKernelGGL((k_dropout_gelu<CFD_B(BWD)>), dim3((unsigned)blocks), dim3(256), 0, st, x, gy, out, n / 4, p, seed, step);
+    }, bwd != 0);
     CFD_LAUNCH_CHECK(what);
     return CFD_OK;
 }

@@ -19,6 +19,7 @@
 //   stage A:    U_re[x][l] = sum_kap S_re cos(th) - D_im sin(th);  U_im[x][l] = sum_kap S_im cos(th) + D_re sin(th)
 //   stage B:    y[x][y] = sum_l (c_l/HW) (U_re cos(2pi l y/W) - U_im sin(2pi l y/W))
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"
 
 #define CFD_WAVES 4  // waves per workgroup (256 threads)
@@ -612,25 +613,11 @@ static bool launch_dft_g(const cfd_plan* p, const TA* x, float* xh, int nimg, in
     const size_t lds = (size_t)p->n_fwd_gv * sizeof(bf16x8) + (size_t)CFD_WAVES * CFD_DFT_OS * sizeof(float2);
     // fp32 storage honours the act_pieces knob; the bf16-storage route keeps two pieces (its values have 8 significant bits)
     const bool ap3 = sizeof(TA) == 4 && cfd_act_pieces() == 3;
-#define CFD_DFTG_P(NJ_, A_, P_)                                                                                        \
-    hipLaunchKernelGGL((k_dft_fwd_g<NJ_, A_, TA, P_>), dim3(blocks), dim3(64 * CFD_WAVES), lds, st, x, (float2*)xh,     \
-                       (const bf16x8*)p->d_fwd_g, p->n_fwd_gv, nimg, p->H, p->W, p->m1, p->m2)
-#define CFD_DFTG(NJ_, A_)                                                             \
-    do {                                                                              \
-        if constexpr (sizeof(TA) == 4) { if (ap3) CFD_DFTG_P(NJ_, A_, 3); else CFD_DFTG_P(NJ_, A_, 2); } \
-        else CFD_DFTG_P(NJ_, A_, 2);                                                  \
-    } while (0)
-#define CFD_DFTG_A(NJ_) do { if (act) CFD_DFTG(NJ_, true); else CFD_DFTG(NJ_, false); } while (0)
-    switch (p->NJG) {
-        case 1: CFD_DFTG_A(1); break;
-        case 2: CFD_DFTG_A(2); break;
-        case 3: CFD_DFTG_A(3); break;
-        case 4: CFD_DFTG_A(4); break;
-        default: CFD_DFTG_A(5); break;
-    }
-#undef CFD_DFTG_A
-#undef CFD_DFTG
-#undef CFD_DFTG_P
+    cfd_dispatch([&](auto NJ, auto A, auto P) {
+        if constexpr (sizeof(TA) == 4 || CFD_I(P) == 2)
+            hipLaunchKernelGGL((k_dft_fwd_g<CFD_I(NJ), CFD_B(A), TA, CFD_I(P)>), dim3(blocks), dim3(64 * CFD_WAVES), lds, st, x, (float2*)xh,
+                               (const bf16x8*)p->d_fwd_g, p->n_fwd_gv, nimg, p->H, p->W, p->m1, p->m2);
+    }, cfd_among<1, 2, 3, 4, 5>(p->NJG), act != 0, cfd_among<3, 2>(ap3 ? 3 : 2));
     return true;
 }
 
@@ -646,12 +633,10 @@ static int launch_dft(const cfd_plan* p, const float* x, float* xh, int nimg, in
 #define CFD_DFT_CAP (3 * 256)
 #endif
             if (blocks > CFD_DFT_CAP) blocks = CFD_DFT_CAP;  // 3 resident workgroups per CU; the waves stride over the images
-#define CFD_DFT64(A_, P_)                                                                                                  \
-    hipLaunchKernelGGL((k_dft_fwd64_b3<CFD_DFT_RING, A_, P_>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh, \
-                       (const bf16x8*)p->d_fwd_b3, nimg, p->m1, p->m2, CfdStemIn{})
-            if (cfd_act_pieces() == 3) { if (act) CFD_DFT64(true, 3); else CFD_DFT64(false, 3); }
-            else { if (act) CFD_DFT64(true, 2); else CFD_DFT64(false, 2); }
-#undef CFD_DFT64
+            cfd_dispatch([&](auto A, auto P) {
+                hipLaunchKernelGGL((k_dft_fwd64_b3<CFD_DFT_RING, CFD_B(A), CFD_I(P)>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
+                                   (const bf16x8*)p->d_fwd_b3, nimg, p->m1, p->m2, CfdStemIn{});
+            }, act != 0, cfd_among<3, 2>(cfd_act_pieces()));
             CFD_LAUNCH_CHECK("cfd_spectral_dft");
             return CFD_OK;
         }
@@ -660,12 +645,10 @@ static int launch_dft(const cfd_plan* p, const float* x, float* xh, int nimg, in
             // 3 workgroups per CU stay resident and the waves stride over the images (measured best of 1..5; a ring of 3
             // k-steps beats a whole image in flight: 23 vs 26 us at B*C = 5120)
             if (blocks > 3 * 256) blocks = 3 * 256;
-            if (act)
-                hipLaunchKernelGGL((k_dft_fwd64<9, 3, true>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
+            with_bools([&](auto A) {
+                hipLaunchKernelGGL((k_dft_fwd64<9, 3, CFD_B(A)>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
                                    (const float*)p->d_fwd, p->n_fwd, nimg, p->H, p->m1, p->m2);
-            else
-                hipLaunchKernelGGL((k_dft_fwd64<9, 3, false>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
-                                   (const float*)p->d_fwd, p->n_fwd, nimg, p->H, p->m1, p->m2);
+            }, act != 0);
             CFD_LAUNCH_CHECK("cfd_spectral_dft");
             return CFD_OK;
         }
@@ -676,12 +659,10 @@ static int launch_dft(const cfd_plan* p, const float* x, float* xh, int nimg, in
     }
     int blocks = (nimg + CFD_WAVES - 1) / CFD_WAVES;
     if (blocks > 2048) blocks = 2048;
-    if (act)
-        hipLaunchKernelGGL((k_dft_fwd<NJ, VEC4, true>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
+    with_bools([&](auto A) {
+        hipLaunchKernelGGL((k_dft_fwd<NJ, VEC4, CFD_B(A)>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
                            (const float*)p->d_fwd, p->n_fwd, nimg, p->H, p->W, p->m1, p->m2, p->KX);
-    else
-        hipLaunchKernelGGL((k_dft_fwd<NJ, VEC4, false>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, x, (float2*)xh,
-                           (const float*)p->d_fwd, p->n_fwd, nimg, p->H, p->W, p->m1, p->m2, p->KX);
+    }, act != 0);
     CFD_LAUNCH_CHECK("cfd_spectral_dft");
     return CFD_OK;
 }
@@ -709,12 +690,10 @@ int cfd_int_spectral_dft_stem(const cfd_plan* p, const float* inputs, const floa
     int blocks = (nimg + CFD_WAVES - 1) / CFD_WAVES;
     if (blocks > 2 * 256) blocks = 2 * 256;  // two resident workgroups per CU (the lifting layer's row weights cost ~40 registers)
     const CfdStemIn si{inputs, mask, cp, w, bias, (const float*)p->d_gx, (const float*)p->d_gy, a0, P, C};
-    if (cfd_act_pieces() == 3)
-        hipLaunchKernelGGL((k_dft_fwd64_b3<1, false, 3, true>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, (const float*)nullptr, (float2*)xh,
+    cfd_dispatch([&](auto P) {
+        hipLaunchKernelGGL((k_dft_fwd64_b3<1, false, CFD_I(P), true>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, (const float*)nullptr, (float2*)xh,
                            (const bf16x8*)p->d_fwd_b3, nimg, p->m1, p->m2, si);
-    else
-        hipLaunchKernelGGL((k_dft_fwd64_b3<1, false, 2, true>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, (const float*)nullptr, (float2*)xh,
-                           (const bf16x8*)p->d_fwd_b3, nimg, p->m1, p->m2, si);
+    }, cfd_among<3, 2>(cfd_act_pieces()));
     CFD_LAUNCH_CHECK("cfd_fno_stem_dft");
     return CFD_OK;
 }
@@ -876,12 +855,9 @@ static void launch_mix(const float2* xin, const float2* w1, const float2* w2, fl
     int BR = (B + nz - 1) / nz;
     BR = (BR + CFD_MIX_SB - 1) / CFD_MIX_SB * CFD_MIX_SB;
     dim3 grid(gx, gy, (B + BR - 1) / BR);
-    if (Cr == CR)
-        hipLaunchKernelGGL((k_mix<CR, WPB, CONJT, true>), grid, dim3(64 * WPB), 0, st, xin, w1, w2, z, B, BR, Cr, Cz,
-                           CoutW, m1, m2);
-    else
-        hipLaunchKernelGGL((k_mix<CR, WPB, CONJT, false>), grid, dim3(64 * WPB), 0, st, xin, w1, w2, z, B, BR, Cr, Cz,
-                           CoutW, m1, m2);
+    with_bools([&](auto X) {  // (X: every contracted channel slot is a real channel)
+        hipLaunchKernelGGL((k_mix<CR, WPB, CONJT, CFD_B(X)>), grid, dim3(64 * WPB), 0, st, xin, w1, w2, z, B, BR, Cr, Cz, CoutW, m1, m2);
+    }, Cr == CR);
 }
 
 // ---- batch-in-lanes mode mixing, weights in LDS -----------------------------------------------------------------
@@ -1001,35 +977,20 @@ static bool launch_mix_lds(const float2* xin, const float2* w1, const float2* w2
     const int BC = 8 * nwv, nchunk = (B + BC - 1) / BC;
     const unsigned grid = (unsigned)((npair * nchunk + 7) / 8) * 16u;
     const size_t lds = (size_t)Cz * Cr * 8 * sizeof(float2);
-    if (Cr == 20)
-        hipLaunchKernelGGL((k_mix_lds<20, CONJT>), dim3(grid), dim3(64 * nwv), lds, st, xin, w1, w2, z, B, BC, Cz, CoutW, M,
-                           m1 * m2, nmg, npair, nchunk);
-    else
-        hipLaunchKernelGGL((k_mix_lds<32, CONJT>), dim3(grid), dim3(64 * nwv), lds, st, xin, w1, w2, z, B, BC, Cz, CoutW, M,
-                           m1 * m2, nmg, npair, nchunk);
+    cfd_dispatch([&](auto CR) {
+        hipLaunchKernelGGL((k_mix_lds<CFD_I(CR), CONJT>), dim3(grid), dim3(64 * nwv), lds, st, xin, w1, w2, z, B, BC, Cz, CoutW, M, m1 * m2, nmg,
+                           npair, nchunk);
+    }, cfd_among<20, 32>(Cr));
     return true;
 }
 
 // (CR, WPB) instantiations: CR >= contracted channels, WPB waves = non-contracted channels per workgroup.
-#define CFD_MIX_DISPATCH(FN, Cr_, Cz_, ...)                                        \
-    do {                                                                            \
-        if ((Cr_) <= 8) FN<8, 8>(__VA_ARGS__);                                      \
-        else if ((Cr_) <= 20 && (Cz_) % 10 == 0) FN<20, 10>(__VA_ARGS__);           \
-        else if ((Cr_) <= 16) FN<16, 8>(__VA_ARGS__);                               \
-        else if ((Cr_) <= 24) FN<24, 8>(__VA_ARGS__);                               \
-        else FN<32, 8>(__VA_ARGS__);                                                \
-    } while (0)
-
-template <int CR, int WPB>
-static void launch_mix_fwd(const float2* a, const float2* b, const float2* c, float2* d, int B, int Cr, int Cz, int CoutW,
-                           int m1, int m2, hipStream_t st) {
-    launch_mix<CR, WPB, false>(a, b, c, d, B, Cr, Cz, CoutW, m1, m2, st);
+// (the contracted side Cr, the other side Cz) -> CR; WPB = 10 with CR = 20, else 8
+static cfd_among_t<8, 20, 16, 24, 32> mix_cr(int Cr, int Cz) {
+    return {Cr <= 8 ? 8 : (Cr <= 20 && Cz % 10 == 0) ? 20 : Cr <= 16 ? 16 : Cr <= 24 ? 24 : 32};
 }
-template <int CR, int WPB>
-static void launch_mix_adj(const float2* a, const float2* b, const float2* c, float2* d, int B, int Cr, int Cz, int CoutW,
-                           int m1, int m2, hipStream_t st) {
-    launch_mix<CR, WPB, true>(a, b, c, d, B, Cr, Cz, CoutW, m1, m2, st);
-}
+template <int CR>
+constexpr int mix_wpb = CR == 20 ? 10 : 8;
 
 extern "C" int cfd_spectral_mix(const cfd_plan* p, const float* xh, const float* w1, const float* w2, float* z, int B,
                                 int Cin, int Cout, int conj_t, void* stream) {
@@ -1045,19 +1006,18 @@ extern "C" int cfd_spectral_mix(const cfd_plan* p, const float* xh, const float*
                16.0 * B * (double)Cin * Cout * p->m1 * p->m2);
     if (cfd_int_modes_mfma_ok(p, B, Cin, Cout, xh, z, w1, false) && ((uintptr_t)w2 % 16) == 0)
         return cfd_int_modes_mix(p, xh, w1, w2, z, B, Cin, conj_t, stream);
-    if (conj_t ? launch_mix_lds<true>((const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr, Cz, Cout,
-                                      p->m1, p->m2, st)
-               : launch_mix_lds<false>((const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr, Cz, Cout,
-                                       p->m1, p->m2, st)) {
+    bool lds_done = false;
+    with_bools([&](auto T) {
+        lds_done = launch_mix_lds<CFD_B(T)>((const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr, Cz, Cout, p->m1, p->m2, st);
+    }, conj_t != 0);
+    if (lds_done) {
         CFD_LAUNCH_CHECK("cfd_spectral_mix(lds)");
         return CFD_OK;
     }
-    if (conj_t)
-        CFD_MIX_DISPATCH(launch_mix_adj, Cr, Cz, (const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr,
-                         Cz, Cout, p->m1, p->m2, st);
-    else
-        CFD_MIX_DISPATCH(launch_mix_fwd, Cr, Cz, (const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr,
-                         Cz, Cout, p->m1, p->m2, st);
+    cfd_dispatch([&](auto CR, auto T) {
+        launch_mix<CFD_I(CR), mix_wpb<CFD_I(CR)>, CFD_B(T)>((const float2*)xh, (const float2*)w1, (const float2*)w2, (float2*)z, B, Cr, Cz, Cout,
+                                                            p->m1, p->m2, st);
+    }, mix_cr(Cr, Cz), conj_t != 0);
     CFD_LAUNCH_CHECK("cfd_spectral_mix");
     return CFD_OK;
 }
@@ -1138,8 +1098,9 @@ template <int CR, int WPB>
 static void launch_spec_wgrad(const float2* xh, const float2* gh, float2* part, int B, int Cin, int Cout, int M,
                               hipStream_t st) {
     dim3 grid((M + 63) / 64, (Cout + WPB - 1) / WPB, (B + CFD_WGRAD_BCHUNK - 1) / CFD_WGRAD_BCHUNK);
-    if (Cin == CR) hipLaunchKernelGGL((k_spec_wgrad_part<CR, WPB, true>), grid, dim3(64 * WPB), 0, st, xh, gh, part, B, Cin, Cout, M);
-    else hipLaunchKernelGGL((k_spec_wgrad_part<CR, WPB, false>), grid, dim3(64 * WPB), 0, st, xh, gh, part, B, Cin, Cout, M);
+    with_bools([&](auto X) {
+        hipLaunchKernelGGL((k_spec_wgrad_part<CR, WPB, CFD_B(X)>), grid, dim3(64 * WPB), 0, st, xh, gh, part, B, Cin, Cout, M);
+    }, Cin == CR);
 }
 
 // ---- register-tiled weight gradient -----------------------------------------------------------------------
@@ -1344,13 +1305,12 @@ static bool launch_spec_wgrad_tile(const float2* xh, const float2* gh, float2* p
     int nmg, npair, BC, nchunk;
     cfd_wgrad_tile_geometry(B, M, &nmg, &npair, &BC, &nchunk);
     const unsigned grid = (unsigned)((npair * nchunk + 7) / 8) * 16u;
-    if (nw <= 8) {
-        if (nw <= 4) hipLaunchKernelGGL((k_spec_wgrad_tile<IT, OT, 4, NS>), dim3(grid), dim3(64 * nw), 0, st, xh, gh, part, B, BC, Cin, Cout, M, nmg, npair, nchunk);
-        else hipLaunchKernelGGL((k_spec_wgrad_tile<IT, OT, 8, NS>), dim3(grid), dim3(64 * nw), 0, st, xh, gh, part, B, BC, Cin, Cout, M, nmg, npair, nchunk);
-    } else if constexpr (IT * OT <= 32) {  // 16 waves: 128 registers per lane
-        if (nw > 16) return false;
-        hipLaunchKernelGGL((k_spec_wgrad_tile<IT, OT, 16, NS>), dim3(grid), dim3(64 * nw), 0, st, xh, gh, part, B, BC, Cin, Cout, M, nmg, npair, nchunk);
-    } else return false;
+    if (nw > 16 || (nw > 8 && IT * OT > 32)) return false;  // 16 waves: 128 registers per lane
+    cfd_dispatch([&](auto NWV) {
+        if constexpr (CFD_I(NWV) != 16 || IT * OT <= 32)
+            hipLaunchKernelGGL((k_spec_wgrad_tile<IT, OT, CFD_I(NWV), NS>), dim3(grid), dim3(64 * nw), 0, st, xh, gh, part, B, BC, Cin, Cout, M, nmg,
+                               npair, nchunk);
+    }, cfd_among<4, 8, 16>(nw <= 4 ? 4 : nw <= 8 ? 8 : 16));
     *nchunk_out = nchunk;
     return true;
 }
@@ -1374,7 +1334,9 @@ extern "C" int cfd_spectral_wgrad(const cfd_plan* p, const float* xh, const floa
         const bool done = launch_spec_wgrad_tile<5, 10, 2>((const float2*)xh, (const float2*)gh, (float2*)ws, B, Cin, Cout, M,
                                                            &nchunk, st);
         if (!done)
-            CFD_MIX_DISPATCH(launch_spec_wgrad, Cin, Cout, (const float2*)xh, (const float2*)gh, (float2*)ws, B, Cin, Cout, M, st);
+            cfd_dispatch([&](auto CR) {
+                launch_spec_wgrad<CFD_I(CR), mix_wpb<CFD_I(CR)>>((const float2*)xh, (const float2*)gh, (float2*)ws, B, Cin, Cout, M, st);
+            }, mix_cr(Cin, Cout));
     }
     CFD_LAUNCH_CHECK("cfd_spectral_wgrad(part)");
     CFD_PROF_W("k_spec_wgrad_reduce", st, 0.0, 0.0);
@@ -1873,25 +1835,11 @@ static bool launch_idft_g(const cfd_plan* p, const float* z, const TADD* addend,
     const size_t lds = (size_t)p->n_inv_gv * sizeof(bf16x8) + (size_t)CFD_WAVES * 2 * CFD_IDFT_ZMAX * sizeof(float);
     constexpr bool all_f32 = sizeof(TA) == 4 && sizeof(TADD) == 4 && sizeof(TPREV) == 4;
     const bool ap3 = all_f32 && cfd_act_pieces() == 3;
-#define CFD_IDG_P(NJ_, E_, P_)                                                                                       \
-    hipLaunchKernelGGL((k_idft_g<NJ_, E_, TA, TADD, TPREV, P_>), dim3(blocks), dim3(64 * CFD_WAVES), lds, st, z, addend, aprev, out,  \
-                       (const bf16x8*)p->d_inv_g, p->n_inv_gv, nimg, p->H, p->W, p->m1, p->m2, p->T, p->SA)
-#define CFD_IDG(NJ_, E_)                                                              \
-    do {                                                                              \
-        if constexpr (all_f32) { if (ap3) CFD_IDG_P(NJ_, E_, 3); else CFD_IDG_P(NJ_, E_, 2); } \
-        else CFD_IDG_P(NJ_, E_, 2);                                                   \
-    } while (0)
-#define CFD_IDG_E(NJ_) do { if (epi == 0) CFD_IDG(NJ_, 0); else if (epi == 1) CFD_IDG(NJ_, 1); else CFD_IDG(NJ_, 2); } while (0)
-    switch (p->NJG) {
-        case 1: CFD_IDG_E(1); break;
-        case 2: CFD_IDG_E(2); break;
-        case 3: CFD_IDG_E(3); break;
-        case 4: CFD_IDG_E(4); break;
-        default: CFD_IDG_E(5); break;
-    }
-#undef CFD_IDG_E
-#undef CFD_IDG
-#undef CFD_IDG_P
+    cfd_dispatch([&](auto NJ, auto E, auto P) {
+        if constexpr (all_f32 || CFD_I(P) == 2)
+            hipLaunchKernelGGL((k_idft_g<CFD_I(NJ), CFD_I(E), TA, TADD, TPREV, CFD_I(P)>), dim3(blocks), dim3(64 * CFD_WAVES), lds, st, z, addend,
+                               aprev, out, (const bf16x8*)p->d_inv_g, p->n_inv_gv, nimg, p->H, p->W, p->m1, p->m2, p->T, p->SA);
+    }, cfd_among<1, 2, 3, 4, 5>(p->NJG), cfd_among<0, 1, 2>(epi), cfd_among<3, 2>(ap3 ? 3 : 2));
     return true;
 }
 
@@ -1906,51 +1854,31 @@ template <int NJ, bool VEC4>
 static int launch_idft(const cfd_plan* p, const float* z, const float* addend, const float* aprev, float* out,
                        int nimg, int epi, hipStream_t st, const CfdReduceTail* tail = nullptr) {
     int blocks = (nimg + CFD_WAVES - 1) / CFD_WAVES;
+    CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
+               (double)nimg * (4.0 * p->H * p->W * (1 + epi) + 16.0 * p->m1 * p->m2), (double)nimg * (8.0 * (p->m1 + 1) * p->W * p->m2 + 4.0 * p->H * p->W * p->m2));
     if constexpr (VEC4) {
         if (idft64_applies(p)) {
             if (blocks > CFD_DFT_CAP) blocks = CFD_DFT_CAP;  // resident workgroups; waves stride over the images
-            CfdReduceTail none{};
-            const bool ap3 = cfd_act_pieces() == 3;
-#define CFD_IDFT64_P(E, P_)                                                                                        \
-    hipLaunchKernelGGL((k_idft64<E, false, P_>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, z, addend, aprev, out,  \
-                       (const bf16x8*)p->d_inv_b3, nimg, p->H, p->m1, p->m2, p->T, p->SA, p->SB, none)
-#define CFD_IDFT64(E) do { if (ap3) CFD_IDFT64_P(E, 3); else CFD_IDFT64_P(E, 2); } while (0)
-            CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
-               (double)nimg * (4.0 * p->H * p->W * (1 + epi) + 16.0 * p->m1 * p->m2), (double)nimg * (8.0 * (p->m1 + 1) * p->W * p->m2 + 4.0 * p->H * p->W * p->m2));
-            if (epi == 0 && tail && tail->nblk > 0) {
-                if (ap3)
-                    hipLaunchKernelGGL((k_idft64<0, true, 3>), dim3(blocks + tail->nblk), dim3(64 * CFD_WAVES), 0, st, z, addend,
-                                       aprev, out, (const bf16x8*)p->d_inv_b3, nimg, p->H, p->m1, p->m2, p->T, p->SA, p->SB, *tail);
-                else
-                    hipLaunchKernelGGL((k_idft64<0, true, 2>), dim3(blocks + tail->nblk), dim3(64 * CFD_WAVES), 0, st, z, addend,
-                                       aprev, out, (const bf16x8*)p->d_inv_b3, nimg, p->H, p->m1, p->m2, p->T, p->SA, p->SB, *tail);
-            }
-            else if (epi == 0) CFD_IDFT64(0);
-            else if (epi == 1) CFD_IDFT64(1);
-            else CFD_IDFT64(2);
-#undef CFD_IDFT64
-#undef CFD_IDFT64_P
+            const bool ride = epi == 0 && tail && tail->nblk > 0;  // (TAIL: the reduction's workgroups behind the transform's)
+            const CfdReduceTail tl = ride ? *tail : CfdReduceTail{};
+            cfd_dispatch([&](auto E, auto TL, auto P) {
+                if constexpr (!CFD_B(TL) || CFD_I(E) == 0)
+                    hipLaunchKernelGGL((k_idft64<CFD_I(E), CFD_B(TL), CFD_I(P)>), dim3(blocks + tl.nblk), dim3(64 * CFD_WAVES), 0, st, z, addend,
+                                       aprev, out, (const bf16x8*)p->d_inv_b3, nimg, p->H, p->m1, p->m2, p->T, p->SA, p->SB, tl);
+            }, cfd_among<0, 1, 2>(epi), ride, cfd_among<3, 2>(cfd_act_pieces()));
             CFD_LAUNCH_CHECK("cfd_spectral_idft");
             return CFD_OK;
         }
     }
-    if (cfd_tune_get(CFD_TUNE_EXACT_FP32) != 1 && cfd_tune_get(CFD_TUNE_GENERAL_B3) != 0 && p->d_inv_g && p->NJG <= 5) {
-        CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
-                   (double)nimg * (4.0 * p->H * p->W * (1 + epi) + 16.0 * p->m1 * p->m2), (double)nimg * (8.0 * (p->m1 + 1) * p->W * p->m2 + 4.0 * p->H * p->W * p->m2));
-        if (launch_idft_g<float>(p, z, addend, aprev, out, nimg, epi, st)) {
-            CFD_LAUNCH_CHECK("cfd_spectral_idft(general)");
-            return CFD_OK;
-        }
+    if (cfd_tune_get(CFD_TUNE_EXACT_FP32) != 1 && cfd_tune_get(CFD_TUNE_GENERAL_B3) != 0 && p->d_inv_g && p->NJG <= 5 &&
+        launch_idft_g<float>(p, z, addend, aprev, out, nimg, epi, st)) {
+        CFD_LAUNCH_CHECK("cfd_spectral_idft(general)");
+        return CFD_OK;
     }
-#define CFD_IDFT_LAUNCH(E)                                                                                         \
-    hipLaunchKernelGGL((k_idft<NJ, VEC4, E>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, z, addend, aprev, out,     \
-                       (const float*)p->d_inv, p->n_inv, nimg, p->H, p->W, p->m1, p->m2, p->T, p->SA, p->SB)
-    CFD_PROF_W(epi == 0 ? "k_idft" : (epi == 1 ? "k_idft_add" : "k_idft_add_dgelu"), st,
-               (double)nimg * (4.0 * p->H * p->W * (1 + epi) + 16.0 * p->m1 * p->m2), (double)nimg * (8.0 * (p->m1 + 1) * p->W * p->m2 + 4.0 * p->H * p->W * p->m2));
-    if (epi == 0) CFD_IDFT_LAUNCH(0);
-    else if (epi == 1) CFD_IDFT_LAUNCH(1);
-    else CFD_IDFT_LAUNCH(2);
-#undef CFD_IDFT_LAUNCH
+    cfd_dispatch([&](auto E) {
+        hipLaunchKernelGGL((k_idft<NJ, VEC4, CFD_I(E)>), dim3(blocks), dim3(64 * CFD_WAVES), 0, st, z, addend, aprev, out,
+                           (const float*)p->d_inv, p->n_inv, nimg, p->H, p->W, p->m1, p->m2, p->T, p->SA, p->SB);
+    }, cfd_among<0, 1, 2>(epi));
     CFD_LAUNCH_CHECK("cfd_spectral_idft");
     return CFD_OK;
 }
@@ -2599,37 +2527,22 @@ static bool launch_block_cfg(const cfd_plan* p, const float* src, const float* z
     long nwg = (long)B * spl;
     if (nd > 1) nwg = (nwg + 7) / 8 * 8 * nd;  // whole groups of 8 * nd block indices (the kernel drops the padding)
     const dim3 grid((unsigned)(nwg + tl.nblk)), block(64 * NW);
-    const bool ap3 = cfd_act_pieces() == 3, gen = block_is_gen(p);
-    const CfdStemG sg0{};
-#define CFD_BLK_P(A_, T_, D_, R_, P_, G_)                                                                                \
-    hipLaunchKernelGGL((k_block<NW, DPW, NCH, A_, T_, D_, R_, P_, G_>), grid, block, 0, st, src, z, w, bias, aprev, dst, \
-                       (const bf16x8*)p->d_inv_b3, Cs, Cd, p->H, p->m1, p->m2, p->T, p->SA, p->SB, tl, spl, p->W, (const float*)p->d_tail, nd, B * spl, sg0)
-    // the lifting-layer sums (k_block<.., STEMG>): plain input gradient of a 64-wide grid, one destination group, at most 24 channels
-    if (stemg && stemg->inputs && trans && !dgelu && !act && nd == 1) {
-        if constexpr (NW * NCH <= 24 && NW != 10) {  // (not the wide (8,2,4) shape: two destination groups; not ten waves: registers)
-#define CFD_BLK_S(R_, P_, G_)                                                                                                   \
-    hipLaunchKernelGGL((k_block<NW, DPW, NCH, false, true, false, R_, P_, G_, true>), grid, block, 0, st, src, z, w, bias, aprev, dst, \
-                       (const bf16x8*)p->d_inv_b3, Cs, Cd, p->H, p->m1, p->m2, p->T, p->SA, p->SB, tl, spl, p->W, (const float*)p->d_tail, nd, B * spl, *stemg)
-#define CFD_BLK_SG(R_, P_) do { if (gen) CFD_BLK_S(R_, P_, true); else CFD_BLK_S(R_, P_, false); } while (0)
-            if (ride) { if (ap3) CFD_BLK_SG(true, 3); else CFD_BLK_SG(true, 2); }
-            else { if (ap3) CFD_BLK_SG(false, 3); else CFD_BLK_SG(false, 2); }
-#undef CFD_BLK_SG
-#undef CFD_BLK_S
-            return true;
-        }
-    }
-#define CFD_BLK(A_, T_, D_, R_)                                                      \
-    do {                                                                             \
-        if (gen) { if constexpr (NW != 10) { if (ap3) CFD_BLK_P(A_, T_, D_, R_, 3, true); else CFD_BLK_P(A_, T_, D_, R_, 2, true); } }  /* launch_block: never (10,2,2) */ \
-        else if (ap3) CFD_BLK_P(A_, T_, D_, R_, 3, false);                           \
-        else CFD_BLK_P(A_, T_, D_, R_, 2, false);                                    \
-    } while (0)
-    if (!trans) { if (act) CFD_BLK(true, false, false, false); else CFD_BLK(false, false, false, false); }
-    else if (ride) { if (dgelu) CFD_BLK(false, true, true, true); else CFD_BLK(false, true, false, true); }
-    else { if (dgelu) CFD_BLK(false, true, true, false); else CFD_BLK(false, true, false, false); }
-#undef CFD_BLK
-#undef CFD_BLK_P
-    return false;
+    // the lifting-layer sums (k_block<.., STEMG>): plain input gradient, one destination group, at most 24 channels (not the wide (8,2,4)
+    // shape: two destination groups; not ten waves: registers)
+    constexpr bool can_sum = NW * NCH <= 24 && NW != 10;
+    const bool sums = can_sum && stemg && stemg->inputs && trans && !dgelu && !act && nd == 1;
+    const CfdStemG sg = sums ? *stemg : CfdStemG{};
+    // A: GELU on the source, T: the transposed (input-gradient) product, D: times gelu'(aprev), R: the tail's workgroups ride, G: general
+    // grid (launch_block: never with the ten waves of (10,2,2)), S: STEMG
+    cfd_dispatch([&](auto A, auto T, auto D, auto R, auto P, auto G, auto S) {
+        constexpr bool live = (CFD_B(T) ? !CFD_B(A) : !CFD_B(D) && !CFD_B(R)) && (!CFD_B(G) || NW != 10) &&
+                              (!CFD_B(S) || (can_sum && CFD_B(T) && !CFD_B(D)));
+        if constexpr (live)
+            hipLaunchKernelGGL((k_block<NW, DPW, NCH, CFD_B(A), CFD_B(T), CFD_B(D), CFD_B(R), CFD_I(P), CFD_B(G), CFD_B(S)>), grid, block, 0, st,
+                               src, z, w, bias, aprev, dst, (const bf16x8*)p->d_inv_b3, Cs, Cd, p->H, p->m1, p->m2, p->T, p->SA, p->SB, tl, spl,
+                               p->W, (const float*)p->d_tail, nd, B * spl, sg);
+    }, !trans && act, trans != 0, trans && dgelu, ride, cfd_among<3, 2>(cfd_act_pieces()), block_is_gen(p), sums);
+    return sums;
 }
 
 // (waves, destination channels per wave, source chunks): waves*DPW >= Cd and waves*NCH >= Cs

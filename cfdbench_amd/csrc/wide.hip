@@ -12,6 +12,7 @@
 //   k_wide_wgrad_part   weight + bias gradients sum_px U[u][px] V[v][px] (1x1 conv, lifting layer, both head layers): pixel tiles
 //                  through LDS, one partial record per workgroup, reduced in a fixed order by k_wide_wgrad_reduce
 #include "cfd_common.h"
+#include "cfd_launch.h"
 #include "cfd_tail.h"  // CFD_HEAD_HD
 
 namespace {
@@ -412,9 +413,10 @@ int wgrad_grid(long npx) {
 size_t wgrad_part_bytes(int G, int NU, int NV) { return (size_t)G * NU * (NV + 1) * sizeof(float); }
 
 void launch_wgrad_part(const float* U, int NU, const WideV& vs, int NV, int B, int HW, float* part, int G, int accumulate, hipStream_t st) {
-    if (NU <= 16) hipLaunchKernelGGL((k_wide_wgrad_part<1, 9>), dim3(G), dim3(256), 0, st, U, NU, vs, NV, B, HW, part, accumulate);
-    else if (NU <= 64 && NV + 1 <= 80) hipLaunchKernelGGL((k_wide_wgrad_part<4, 5>), dim3(G), dim3(256), 0, st, U, NU, vs, NV, B, HW, part, accumulate);
-    else hipLaunchKernelGGL((k_wide_wgrad_part<8, 9>), dim3(G), dim3(256), 0, st, U, NU, vs, NV, B, HW, part, accumulate);
+    // (rows of U per tile; a tile of four rows takes five columns of V, the others nine)
+    cfd_dispatch([&](auto TU) {
+        hipLaunchKernelGGL((k_wide_wgrad_part<CFD_I(TU), CFD_I(TU) == 4 ? 5 : 9>), dim3(G), dim3(256), 0, st, U, NU, vs, NV, B, HW, part, accumulate);
+    }, cfd_among<1, 4, 8>(NU <= 16 ? 1 : (NU <= 64 && NV + 1 <= 80) ? 4 : 8));
 }
 void launch_wgrad_reduce(const float* part, int G, int NU, int NV, float* gw, float* gb, hipStream_t st) {
     const int n = NU * (NV + 1);
@@ -439,13 +441,9 @@ int cfd_int_wide_mix(const cfd_plan* p, const float* xh, const float* w1, const 
                8.0 * B * (double)Cin * Cout * M);
     const COp A{(const float2*)xh, nullptr, (long)Cr * M, (long)M};
     const COut O{(float2*)z, nullptr, (long)Cz * M, (long)M};
-    if (conj_t) {
-        const COp W{(const float2*)w1, (const float2*)w2, (long)Cout * half, (long)half};  // (row = i, k = o)
-        launch_cgemm<false, true>(A, W, O, B, Cr, Cz, M, half, nullptr, p->m2, st);
-    } else {
-        const COp W{(const float2*)w1, (const float2*)w2, (long)half, (long)Cout * half};  // (row = o, k = i)
-        launch_cgemm<false, false>(A, W, O, B, Cr, Cz, M, half, nullptr, p->m2, st);
-    }
+    // (conj_t: row = i, k = o; else row = o, k = i)
+    const COp W{(const float2*)w1, (const float2*)w2, conj_t ? (long)Cout * half : (long)half, conj_t ? (long)half : (long)Cout * half};
+    with_bools([&](auto T) { launch_cgemm<false, CFD_B(T)>(A, W, O, B, Cr, Cz, M, half, nullptr, p->m2, st); }, conj_t != 0);
     CFD_LAUNCH_CHECK("cfd_spectral_mix(wide)");
     return CFD_OK;
 }
@@ -470,8 +468,9 @@ int cfd_int_wide_chanmix(const float* in, const float* w, const float* bias, flo
     const dim3 grid((unsigned)grid_blocks((long)B * HW, 2048), (unsigned)((Co + WIDE_OC - 1) / WIDE_OC));
     CFD_PROF_W(transpose ? "k_wide_chanmix_t" : (act_in ? "k_wide_chanmix_act" : "k_wide_chanmix"), st,
                4.0 * B * HW * ((double)Ci * grid.y + Co), 2.0 * B * HW * (double)Ci * Co);
-    if (act_in) hipLaunchKernelGGL(k_wide_chanmix<true>, grid, dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose, dgelu);
-    else hipLaunchKernelGGL(k_wide_chanmix<false>, grid, dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose, dgelu);
+    with_bools([&](auto A) {
+        hipLaunchKernelGGL(k_wide_chanmix<CFD_B(A)>, grid, dim3(256), 0, st, in, w, bias, out, B, Ci, Co, HW, transpose, dgelu);
+    }, act_in != 0);
     CFD_LAUNCH_CHECK("cfd_chanmix(wide)");
     return CFD_OK;
 }
@@ -517,12 +516,11 @@ int cfd_int_wide_head_bwd(const float* a, const float* mask, const float* label,
         const int nb = B - b0 < bc ? B - b0 : bc;
         const size_t ea = (size_t)b0 * C * HW, eo = (size_t)b0 * Co * HW;
         CFD_PROF_W("k_wide_head_bwd_px", st, 4.0 * nb * HW * (C + 4.0 * CFD_HEAD_HD + 3.0 * Co), 2.0 * nb * HW * (double)CFD_HEAD_HD * (C + Co));
-#define CFD_WHB(CM, A_) do { if (Co <= 2) CFD_WHB_N(CM, A_, 2); else CFD_WHB_N(CM, A_, 8); } while (0)
-#define CFD_WHB_N(CM, A_, N_)                                                                                                                  hipLaunchKernelGGL((k_wide_head_bwd_px<CM, A_, N_>), dim3(grid_blocks((long)nb * HW, 2048)), dim3(256), 0, st, a + ea, mask ? mask + (size_t)b0 * HW : nullptr,                            label ? label + eo : nullptr, preds ? preds + eo : nullptr, gext ? gext + eo : nullptr, coef, w1, b1, w2, zbuf, hbuf, dout, nb, C, Co, HW)
-        if (C <= 64) { if (act_in) CFD_WHB(64, true); else CFD_WHB(64, false); }
-        else { if (act_in) CFD_WHB(128, true); else CFD_WHB(128, false); }
-#undef CFD_WHB
-#undef CFD_WHB_N
+        cfd_dispatch([&](auto CM, auto A, auto N) {
+            hipLaunchKernelGGL((k_wide_head_bwd_px<CFD_I(CM), CFD_B(A), CFD_I(N)>), dim3(grid_blocks((long)nb * HW, 2048)), dim3(256), 0, st, a + ea,
+                               mask ? mask + (size_t)b0 * HW : nullptr, label ? label + eo : nullptr, preds ? preds + eo : nullptr,
+                               gext ? gext + eo : nullptr, coef, w1, b1, w2, zbuf, hbuf, dout, nb, C, Co, HW);
+        }, cfd_among<64, 128>(C <= 64 ? 64 : 128), act_in != 0, cfd_among<2, 8>(Co <= 2 ? 2 : 8));
         CFD_LAUNCH_CHECK("cfd_fno_head_bwd(wide px)");
         // d loss / d a = W1^T dz (* gelu'(a) where the head reads GELU(a))
         CFD_TRY(cfd_int_wide_chanmix(zbuf, w1, nullptr, ga + ea, nb, CFD_HEAD_HD, C, HW, 0, 1, stream, act_in ? a + ea : nullptr));
@@ -579,16 +577,10 @@ int cfd_int_wide_head_fwd(const float* a, const float* mask, const float* label,
     const int blocks = grid_blocks((long)B * HW, WIDE_HEAD_BLOCKS);
     float* part = label ? (float*)ws : nullptr;
     CFD_PROF_W("k_wide_head", st, B * HW * (4.0 * C + 4.0 * (1 + (label ? 2 : 1) * Co)), 2.0 * B * HW * (double)CFD_HEAD_HD * (C + Co));
-#define CFD_WH_N(CM, N_)                                                                                                         \
-    do {                                                                                                                         \
-        if (act_in) hipLaunchKernelGGL((k_wide_head<CM, true, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
-        else hipLaunchKernelGGL((k_wide_head<CM, false, N_>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part, B, C, Co, HW); \
-    } while (0)
-#define CFD_WH(CM) do { if (Co <= 2) CFD_WH_N(CM, 2); else CFD_WH_N(CM, 8); } while (0)  // out_chan 3 .. 8: eight accumulators
-    if (C <= 64) CFD_WH(64);
-    else CFD_WH(128);
-#undef CFD_WH
-#undef CFD_WH_N
+    cfd_dispatch([&](auto CM, auto A, auto N) {  // (out_chan 3 .. 8: eight accumulators)
+        hipLaunchKernelGGL((k_wide_head<CFD_I(CM), CFD_B(A), CFD_I(N)>), dim3(blocks), dim3(256), 0, st, a, mask, label, w1, b1, w2, b2, preds, part,
+                           B, C, Co, HW);
+    }, cfd_among<64, 128>(C <= 64 ? 64 : 128), act_in != 0, cfd_among<2, 8>(Co <= 2 ? 2 : 8));
     CFD_LAUNCH_CHECK("cfd_fno_head_fwd(wide)");
     if (label) {
         hipLaunchKernelGGL(k_wide_loss_final, dim3(1), dim3(64), 0, st, (const float*)part, blocks, (float)((double)B * Co * HW), sums,

@@ -13,8 +13,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 #include <tuple>
 #include <vector>
+
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <link.h>
+#include <unistd.h>
 
 #define CFD_EMUL 1
 #define __global__
@@ -129,8 +136,70 @@ inline void fiber_entry() {
 template <typename F, typename Tup, size_t... I>
 void call(F f, Tup& t, std::index_sequence<I...>) { f(std::get<I>(t)...); }
 
+// Opt-in launch log (tools/emul_launch_digest.py): with CFD_EMUL_LAUNCH_LOG=<path> in the environment (read once) every launch appends
+// "<kernel instantiation> grid x y z block x y z lds bytes".  The instantiation is the demangled symbol at the function's address, looked
+// up in the symbol table of the library file itself, so that the kernels in anonymous namespaces (wide.hip, ingrad.hip: no dynamic symbol)
+// are named with their template arguments too; without a symbol table the launch site's spelling is logged, marked "?".  A "%p" in the
+// path becomes the process id (tests that run their cases in parallel child processes: one file per process).
+// name of the function at `addr` from the symbol table of the file that holds it (local symbols too), "" if none
+inline std::string local_symbol(const void* addr) {
+    static std::map<std::string, std::map<uintptr_t, std::string>> files;  // file -> (offset -> mangled name), read once per file
+    Dl_info di;
+    if (!dladdr(addr, &di) || !di.dli_fname) return "";
+    auto it = files.find(di.dli_fname);
+    if (it == files.end()) {
+        it = files.emplace(di.dli_fname, std::map<uintptr_t, std::string>{}).first;
+        if (FILE* fp = fopen(di.dli_fname, "rb")) {
+            ElfW(Ehdr) eh;
+            std::vector<ElfW(Shdr)> sh;
+            if (fread(&eh, sizeof eh, 1, fp) == 1 && eh.e_shentsize == sizeof(ElfW(Shdr))) {
+                sh.resize(eh.e_shnum);
+                fseek(fp, (long)eh.e_shoff, SEEK_SET);
+                if (fread(sh.data(), sizeof(ElfW(Shdr)), sh.size(), fp) != sh.size()) sh.clear();
+            }
+            for (const auto& s : sh) {
+                if (s.sh_type != SHT_SYMTAB || s.sh_link >= sh.size()) continue;
+                std::vector<ElfW(Sym)> syms(s.sh_size / sizeof(ElfW(Sym)));
+                std::vector<char> str(sh[s.sh_link].sh_size + 1, 0);
+                fseek(fp, (long)s.sh_offset, SEEK_SET);
+                if (fread(syms.data(), sizeof(ElfW(Sym)), syms.size(), fp) != syms.size()) continue;
+                fseek(fp, (long)sh[s.sh_link].sh_offset, SEEK_SET);
+                if (fread(str.data(), 1, str.size() - 1, fp) != str.size() - 1) continue;
+                for (const auto& y : syms)
+                    if (ELF64_ST_TYPE(y.st_info) == STT_FUNC && y.st_value && y.st_name < str.size()) it->second[y.st_value] = &str[y.st_name];
+            }
+            fclose(fp);
+        }
+    }
+    const auto hit = it->second.find((uintptr_t)addr - (uintptr_t)di.dli_fbase);
+    return hit == it->second.end() ? "" : hit->second;
+}
+inline void log_launch(const void* kern, const char* spelled, dim3 grid, dim3 block, size_t shmem) {
+    static FILE* const f = []() -> FILE* {
+        const char* env = getenv("CFD_EMUL_LAUNCH_LOG");
+        if (!env || !*env) return nullptr;
+        std::string path(env);
+        if (const size_t at = path.find("%p"); at != std::string::npos) path.replace(at, 2, std::to_string((long)getpid()));
+        return fopen(path.c_str(), "a");
+    }();
+    if (!f) return;
+    std::string name = local_symbol(kern);
+    if (name.empty()) {
+        name = std::string("?") + spelled;
+    } else {
+        int status = 0;
+        if (char* d = abi::__cxa_demangle(name.c_str(), nullptr, nullptr, &status)) {  // (an extern "C" kernel keeps its name)
+            name = d;
+            free(d);
+        }
+    }
+    fprintf(f, "%s grid %u %u %u block %u %u %u lds %zu\n", name.c_str(), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
+    fflush(f);
+}
+
 template <typename... KArgs, typename... Args>
-void launch(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
+void launch(const char* spelled, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
+    log_launch((const void*)kern, spelled, grid, block, shmem);
     static std::tuple<KArgs...>* s_args;
     static void (*s_kern)(KArgs...);
     static long s_nblocks;
@@ -213,7 +282,7 @@ void launch(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t shmem, hipStre
 #define blockDim (cfd_emul::g_blockDim)
 #define gridDim (cfd_emul::g_gridDim)
 #define hipLaunchKernelGGL(kern, grid, block, shmem, stream, ...) \
-    cfd_emul::launch(kern, dim3(grid), dim3(block), shmem, stream, __VA_ARGS__)
+    cfd_emul::launch(#kern, kern, dim3(grid), dim3(block), shmem, stream, __VA_ARGS__)
 
 inline void __syncthreads() { cfd_emul::block_sync(); }
 
