@@ -21,6 +21,15 @@ CFD_STEP_DECOUPLED_WD = 32  # AdamW: param[i] *= 1 - lr * weight_decay, then Ada
 CFD_STEP_SKIP_NONFINITE = 64
 CFD_CLIP_SKIPPED = CFD_CLIP_FLOATS - 1      # skipped steps since the caller zeroed it
 CFD_CLIP_CONSECUTIVE = CFD_CLIP_FLOATS - 2  # skipped steps since the last applied one
+# cfd_objective_fwd / cfd_objective_bwd (include/cfdbench_amd.h, "Training objectives")
+CFD_OBJ_REL_L2, CFD_OBJ_NMSE_SAMPLE, CFD_OBJ_NMSE_CHANNEL = 0, 1, 2
+CFD_OBJ_MAX_PARTS = 8
+OBJECTIVE_IDS = {"rel_l2": CFD_OBJ_REL_L2, "nmse_sample": CFD_OBJ_NMSE_SAMPLE, "nmse_channel": CFD_OBJ_NMSE_CHANNEL}
+
+
+def CFD_OBJ_REC_FLOATS(B: int, Co: int) -> int:
+    """Floats of the `rec` buffer of cfd_objective_fwd / _bwd: the header's macro of the same name."""
+    return 8 + 4 * max(int(B), int(Co)) + 4 * int(B) * int(Co) * CFD_OBJ_MAX_PARTS
 
 
 class CfdError(RuntimeError):
@@ -188,6 +197,8 @@ _SIGS = {
                               _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cfd_fno_backward_phase": (_I, [_P, C.POINTER(FnoShape), C.POINTER(FnoParams), C.POINTER(FnoParams),
                               _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "cfd_objective_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "cfd_objective_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
 }
 
 

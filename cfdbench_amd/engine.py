@@ -30,7 +30,7 @@ from torch import Tensor
 
 from . import _lib
 from ._capi import (CFD_CLIP_CONSECUTIVE, CFD_CLIP_FLOATS, CFD_CLIP_SKIPPED, CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE, CFD_STEP_DECOUPLED_WD,
-                    CFD_STEP_SKIP_NONFINITE)
+                    CFD_STEP_SKIP_NONFINITE, CFD_OBJ_REC_FLOATS, OBJECTIVE_IDS)
 from .functional import _param_struct
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
@@ -352,7 +352,7 @@ class FnoTrainEngine:
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
                  overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None,
                  trainable: Optional[Sequence[str]] = None, optimizer: str = "adam", skip_nonfinite: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, objective: Optional[str] = None):
         """``trainable``: state_dict key prefixes (``{"fc1", "fc2"}``, ``{"blocks.3", "fc1", "fc2"}``) of the parameters to train; the
         others are frozen (their ``requires_grad`` is set to match).  None: the engine honours ``requires_grad`` as it finds it.  The
         flat buffers (parameters, gradient, moments, accumulator, what a data-parallel run exchanges) hold the trainable tensors only, and
@@ -394,6 +394,17 @@ class FnoTrainEngine:
         parallel, every rank applies the same bits, so the replicas' averages stay identical with no collective.  ``ema_state_dict()``
         and ``averaged()`` read it; ``state_dict()`` carries it.
 
+        ``objective`` = "rel_l2" | "nmse_sample" | "nmse_channel" (None: today's engine, call for call): what the step MINIMISES, beside
+        what it reports (include/cfdbench_amd.h, "Training objectives": the per-sample relative L2 norm -- LpLoss().rel of the reference's
+        FNO directory --, nMSE per sample, nMSE per channel).  A pass is then cfd_fno_forward (training; it still fills the loss sums, so
+        ``scores()`` and the returned sums keep reporting mse / nmse), cfd_objective_fwd, cfd_objective_bwd into a per-shape gradient on
+        the predictions, and the backward phases entered with that buffer as ``gpreds_ext`` (label = NULL, flags = 0); the gradient is
+        final before the unchanged optimiser call, so clipping, ``skip_nonfinite``, EMA, AdamW, frozen subsets, accumulation groups and
+        rollout windows (step k's 1 / K rides in ``upstream``, the chained input gradient of step k + 1 enters as ``gadd``) work as they
+        do.  Nothing is deferred and the one-pass head is not used: ``loss_name`` must stay "nmse" and bf16 activation storage is
+        refused (ValueError).  Data-parallel runs exchange once behind the pass, each rank's objective over its own batch.
+        ``objective_value()`` is the device scalar of the last pass ((K,) for a window).
+
         ``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
         activations a_0 .. a_L are rounded to bf16 when stored -- half the bytes of what the backward pass re-reads -- and the
         backward pass reads those rounded values; master weights, gradients, accumulation and Adam stay fp32
@@ -405,6 +416,14 @@ class FnoTrainEngine:
         self.act_dtype = _ACT_DTYPES[act_dtype]
         if self.act_dtype and not fused_head:
             raise ValueError("bf16 activation storage runs the one-pass training head: fused_head must be True")
+        if objective is not None:
+            if objective not in OBJECTIVE_IDS:
+                raise ValueError(f"objective must be None or one of {sorted(OBJECTIVE_IDS)}")
+            if loss_name != "nmse":
+                raise ValueError("an objective replaces the loss the step minimises; the reported loss stays nmse: loss_name must be 'nmse'")
+            if self.act_dtype:
+                raise ValueError("an objective runs the two-pass head: bf16 activation storage (the one-pass head) is not available")
+        self.objective = objective
         if optimizer not in ("adam", "adamw"):
             raise ValueError("optimizer must be 'adam' or 'adamw'")
         self.optimizer = optimizer
@@ -448,7 +467,9 @@ class FnoTrainEngine:
         # With the flags, `flat.grad` after train_step holds the gradients of sum d^2 * upstream / n (nmse); `gradients()` rescales.
         # A trainable subset keeps the flags whose carrier still runs and whose result has a place (mask_defer_flags).  The normaliser's
         # flag is never dropped, so what reads `_route_defers` (optimizer_step, for gradients()) holds for a subset as it is.
-        self.defer_flags = mask_defer_flags(0 if (self.sync.exchange or not fused_head) else 7, mask[0], self.last_phase)
+        # (an objective's gradient enters the backward pass from outside: nothing is deferred)
+        self.defer_flags = mask_defer_flags(0 if (self.sync.exchange or not fused_head or objective is not None) else 7, mask[0],
+                                            self.last_phase)
         self._route_defers = False  # whether the batch's route honours the flags: known per batch (_prepare, _lib.fno_call)
         self.sums = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.coef = torch.zeros(2, dtype=torch.float32, device=self.device)
@@ -495,14 +516,49 @@ class FnoTrainEngine:
             raise RuntimeError("cfd_fno_workspace_bytes_ex returned 0 for this shape / activation type")
         self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         self.preds = torch.empty((B, c["out_chan"], H, W), dtype=torch.float32, device=self.device)
+        if self.objective is not None:  # (per shape, like preds: a captured graph replays on these addresses)
+            self._obj_rec = torch.empty(CFD_OBJ_REC_FLOATS(B, c["out_chan"]), dtype=torch.float32, device=self.device)
+            self._obj_gpreds = torch.empty_like(self.preds)
+            self._obj_value = torch.zeros((), dtype=torch.float32, device=self.device)
+            self._obj_last = self._obj_value
         self._shape_key = key
         self._graph = None
+
+    def _objective_backward(self, plan, sh, pr, gr, data, sums, ws, st, value: Tensor, last_phase: int, gadd: Optional[int] = None,
+                            upstream: float = 1.0) -> None:
+        """Behind a training forward pass: the objective's value into ``value``, its gradient on the predictions times ``upstream`` (plus ``gadd``,
+        the device address of a gradient to add, or None) into the per-shape buffer, and the backward phases 0 .. last_phase entered with it (label = NULL, no loss
+        coefficients, flags = 0; the mse id: at flags = 0 the route rule does not read ``which``)."""
+        a = self.api
+        inputs, cp, mk, label, preds = data
+        B, Co, HW = self.shape.B, self.shape.out_chan, self.shape.H * self.shape.W
+        kind, rec, gp = OBJECTIVE_IDS[self.objective], self._obj_rec.data_ptr(), self._obj_gpreds.data_ptr()
+        a.call("cfd_objective_fwd", preds, label, mk, rec, value.data_ptr(), B, Co, HW, kind, st)
+        a.call("cfd_objective_bwd", preds, label, mk, rec, gadd, None, float(upstream), gp, B, Co, HW, kind, st)
+        for phase in range(last_phase + 1):
+            a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, inputs, cp, mk, None, preds, gp, None, sums, ws, phase, _LOSS_IDS["mse"], 0,
+                   0, st)
+
+    def objective_value(self) -> Tensor:
+        """Device tensor (no sync): the objective of the last pass -- 0-dim; after a rollout window (K,), one value per step."""
+        if self.objective is None:
+            raise RuntimeError("FnoTrainEngine.objective_value: the engine was built without objective")
+        if getattr(self, "_obj_last", None) is None:
+            raise RuntimeError("FnoTrainEngine.objective_value: no pass has run")
+        return self._obj_last
 
     def forward_backward(self, inputs: Tensor, label: Tensor, case_params: Tensor, mask: Optional[Tensor] = None, flags: int = 0):
         """Enqueue forward + loss + backward into the flat gradient buffer (every gradient is overwritten).  ``flags`` =
         CFD_TRAIN_DEFER_* (train_step passes ``defer_flags``): the gradients are then complete only after ``optimizer_step``'s launch."""
         a = self.api
         model, data, sums, coef, ws, st = self._begin(inputs, label, case_params, mask, flags)
+        if self.objective is not None:
+            if flags:
+                raise RuntimeError("FnoTrainEngine: a pass with an objective defers nothing (flags must be 0)")
+            a.call("cfd_fno_forward", *model[:3], *data, sums, ws, 1, st)
+            self._objective_backward(*model, data, sums, ws, st, self._obj_value, self.last_phase)
+            self._obj_last = self._obj_value
+            return
         if self.fused_head:
             a.call("cfd_fno_forward_train_f", *model, *data, sums, coef, ws, self.loss_id, 1.0, self.act_dtype, flags, st)
             # phase 0 (the head) left the fused kernel already; a trainable subset stops behind its shallowest tensor's phase
@@ -629,6 +685,8 @@ class FnoTrainEngine:
         if getattr(self, "_win_key", None) != key:
             self._win = dict(preds=[torch.empty_like(self.preds) for _ in range(K)],
                              sums=torch.zeros((K, 4), dtype=torch.float32, device=self.device))
+            if self.objective is not None:
+                self._win["obj"] = torch.zeros(K, dtype=torch.float32, device=self.device)
             self._win_key = key
         w = self._win
         if full and "ws" not in w:
@@ -678,15 +736,19 @@ class FnoTrainEngine:
             return sums.view(1, 4)
         w = self._window_state(inputs, case_params, K, full=not detach)
         if detach:
-            own = (self.preds, self.sums)
+            own = (self.preds, self.sums, getattr(self, "_obj_value", None))
             try:
                 x = inputs
                 for k in range(K):  # step k + 1 reads preds_k while it writes preds_{k+1}: every step has its own buffer (and sums row)
                     self.preds, self.sums = w["preds"][k], w["sums"][k]
+                    if self.objective is not None:
+                        self._obj_value = w["obj"][k]
                     self.accumulate(x, labels_seq[k], case_params, mask, weight=weight / K, first=first and k == 0)
                     x = w["preds"][k]
             finally:
-                self.preds, self.sums = own
+                self.preds, self.sums, self._obj_value = own
+            if self.objective is not None:
+                self._obj_last = w["obj"]
             self._win_last = w["preds"]
             return w["sums"]
         a, st = self.api, torch.cuda.current_stream().cuda_stream
@@ -703,7 +765,9 @@ class FnoTrainEngine:
 
         for k in range(K):
             gr, data, sums, coef, ws = args(k)
-            if k == K - 1 and self.fused_head:  # no chained gradient on the last step: the head runs once for both directions
+            if self.objective is not None:  # (the loss sums for the report; the objective itself runs in front of each backward pass)
+                a.call("cfd_fno_forward", plan, sh, pr, *data, sums, ws, 1, st)
+            elif k == K - 1 and self.fused_head:  # no chained gradient on the last step: the head runs once for both directions
                 a.call("cfd_fno_forward_train_f", plan, sh, pr, gr, *data, sums, coef, ws, self.loss_id, 1.0 / K, 0, 0, st)
                 one_pass[k] = True
             else:
@@ -713,14 +777,20 @@ class FnoTrainEngine:
             gr, data, sums, coef, ws = args(k)
             gext = w["dx"][k % 2].data_ptr() if k < K - 1 else None  # = d_inputs of step k + 1 (1-based k + 2: dx[(k + 2) % 2])
             # step k + 1 >= 2 hands d loss / d x back to the step before it: every phase; the window's first step stops where a plain pass does
-            for phase in range(1 if one_pass[k] else 0, (self.L + 1 if k >= 1 else self.last_phase) + 1):
-                a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *data, gext, coef, sums, ws, phase, self.loss_id, 0, 0, st)
+            last = self.L + 1 if k >= 1 else self.last_phase
+            if self.objective is not None:  # (the chained gradient is added where the objective's is written: gpreds_ext is their sum)
+                self._objective_backward(plan, sh, pr, gr, data, sums, ws, st, w["obj"][k], last, gadd=gext, upstream=1.0 / K)
+            else:
+                for phase in range(1 if one_pass[k] else 0, last + 1):
+                    a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, *data, gext, coef, sums, ws, phase, self.loss_id, 0, 0, st)
             flags = CFD_STEP_ACCUMULATE | (CFD_STEP_ACCUM_INIT if (first and k == K - 1) else 0)
             self._adam_step(self.astruct, w["gs"][k], self.accum, self.flat.grad, False, float(weight), flags, xs[k], case_params, mask,
                             w["sums"][k], w["ws"][k])  # (act_dtype is 0 here: bf16 storage was refused above)
         self._last = (inputs, case_params, mask, 0)
         self._accum_open = True
         self._win_last = w["preds"]
+        if self.objective is not None:
+            self._obj_last = w["obj"]
         return w["sums"]
 
     def train_window(self, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None,
@@ -856,7 +926,8 @@ class FnoTrainEngine:
         batch (no host sync -- read it with .tolist() only when logging)."""
         self._no_open_group("train_step")
         # (a frozen subset exchanges its compact gradient once, behind the pass: the per-phase exchange is the all-trainable engine's)
-        if self.sync.exchange and self.overlap and self.all_trainable:
+        # (so does an objective: its pass has no per-phase entry of its own)
+        if self.sync.exchange and self.overlap and self.all_trainable and self.objective is None:
             scale = self.forward_backward_overlapped(inputs, label, case_params, mask)
         else:
             self.forward_backward(inputs, label, case_params, mask, self.defer_flags)
@@ -923,6 +994,7 @@ class FnoTrainEngine:
         # Round 6: over RCCL the per-phase all-reduces are captured with the pass (forked onto the communicator's stream and joined back
         # by events), so a replayed data-parallel step makes no host call into the process group; host-staged backends reduce after it.
         self._graph_exchanges = bool(self.sync.exchange and self.sync.device_native and self.overlap and self.all_trainable
+                                     and self.objective is None
                                      and os.environ.get("CFDBENCH_DP_ONE_GRAPH", "1") != "0")
         with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
             if self._graph_exchanges:

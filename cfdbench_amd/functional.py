@@ -12,7 +12,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._capi import FnoParams
+from ._capi import OBJECTIVE_IDS, FnoParams
 
 
 def _require_cuda(*ts: Optional[Tensor]):
@@ -286,6 +286,16 @@ def mse_loss_scores(preds: Tensor, labels: Tensor, normalize: bool) -> dict:
     if normalize:
         out["nmse"] = nmse
     return out
+
+
+def objective_loss(preds: Tensor, labels: Tensor, kind: str, mask: Optional[Tensor] = None) -> Tensor:
+    """``kind`` = "rel_l2" (LpLoss(d=2, p=2).rel of the reference's src/models/fno/utilities3.py: the mean over the batch of
+    ||preds - labels * mask|| / ||labels * mask||), "nmse_sample" or "nmse_channel"; preds, labels (B, C, ...), mask one value per sample
+    and pixel ((B, ...), (B, 1, ...)) or None.  A 0-dim tensor, differentiable in ``preds``."""
+    if kind not in OBJECTIVE_IDS:
+        raise NotImplementedError(f"objective {kind!r}: one of {sorted(OBJECTIVE_IDS)}")
+    from .objective import ObjectiveLossFn  # (the node lives beside its kernels' binding: cfdbench_amd/objective.py)
+    return ObjectiveLossFn.apply(preds, labels, mask, OBJECTIVE_IDS[kind])
 
 
 def scores_from_sums(sums: Tensor, normalize: bool) -> dict:

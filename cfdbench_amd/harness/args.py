@@ -44,7 +44,11 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     average; 0.0 = off; not with --graph 1),
     ``ema_warmup`` (1: the decay of optimiser step t is min(D, (1 + t) / (10 + t))),
     ``ema_eval`` (1: validation and the final test run on the averaged weights; the trained ones are back afterwards; the multi-step
-    rollout of the averaged weights is ``python -m cfdbench_amd.harness.multistep_ema``, which takes test_multistep's flags).
+    rollout of the averaged weights is ``python -m cfdbench_amd.harness.multistep_ema``, which takes test_multistep's flags),
+    ``objective`` (train_auto, the fno model: what the step MINIMISES -- nmse = the reference's loop, unchanged | rel_l2 = the per-sample
+    relative L2 norm, LpLoss(d=2, p=2).rel of the reference's src/models/fno/utilities3.py | nmse_sample | nmse_channel; --fused 1:
+    FnoTrainEngine(objective=), eager: ``loss.ObjectiveLoss``; the loss history and the log line carry its value beside nmse, dev_loss
+    and the checkpoint choice stay on nmse; not with --graph 1 or --dtype bf16).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -76,10 +80,11 @@ _FLAGS: Dict[str, Any] = dict(
     infer_steps=20, fused=0, plot_interval=1, resume=0, device_loader=0, dtype="fp32", graph=0,
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
     fused_accumulation_steps=1, unroll_detach=0, freeze="", train_only="", optimizer="adam", init_from="",
-    skip_nonfinite=0, max_consecutive_skips=100, ema_decay=0.0, ema_warmup=0, ema_eval=0,
+    skip_nonfinite=0, max_consecutive_skips=100, ema_decay=0.0, ema_warmup=0, ema_eval=0, objective="nmse",
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
+OBJECTIVES = ("nmse", "rel_l2", "nmse_sample", "nmse_channel")  # --objective: nmse = today's loop
 _OPTIONAL_INT = ("fno_padding",)  # flags whose default is None: parsed as int when given
 
 
@@ -166,6 +171,12 @@ def is_args_valid(args: Args) -> None:
         assert not args.ema_warmup and not args.ema_eval, "--ema_warmup / --ema_eval are options of --ema_decay D > 0"
     if args.graph:
         assert not args.ema_decay > 0.0, "--graph 1 with --ema_decay is not built: cfd_adam_multi has no averaged form"
+    assert args.objective in OBJECTIVES, f"--objective is one of {', '.join(OBJECTIVES)}"
+    if args.objective != "nmse":
+        assert args.model == "fno", "--objective other than nmse is built for the fno model (its gradient enters Fno2d's backward pass)"
+        assert not args.graph, "--graph 1 with an --objective is not built: the captured step backpropagates loss['nmse']"
+        assert args.dtype == "fp32", "--dtype bf16 with an --objective is not built: bf16 storage runs the one-pass head"
+        assert args.loss_name == "nmse", "an --objective keeps --loss_name nmse for the reported scores"
     assert args.unet_insert_case_params_at in ("input", "hidden")
     if args.fno_padding is not None:
         assert args.model == "fno", "--fno_padding is Fno2d's domain padding"

@@ -33,6 +33,8 @@ def get_output_dir(args, is_auto: bool = False) -> Path:
         name = f"lr{args.lr}_d{args.fno_depth}_h{args.fno_hidden_dim}_m1{args.fno_modes_x}_m2{args.fno_modes_y}"
         if getattr(args, "fno_padding", None) is not None:  # (only when set: every run without padding keeps its directory)
             name += f"_pad{args.fno_padding}"
+        if getattr(args, "objective", "nmse") != "nmse":  # (likewise: a run on another objective gets a directory of its own)
+            name += f"_obj-{args.objective}"
     elif m == "resnet":
         name = f"lr{args.lr}_d{args.resnet_depth}_w{args.resnet_hidden_chan}"
     elif m == "auto_edeeponet":

@@ -32,7 +32,8 @@ from ..engine import FnoTrainEngine, sync_gradients
 from ..models.base_model import AutoCfdModel
 from ..models.fno.fno2d import Fno2d
 from ..unroll import collate_windows, unroll_windows, unrolled_loss
-from .args import Args, is_args_valid
+from ..models.loss import objective_to_fn
+from .args import OBJECTIVES, Args, is_args_valid
 from .autoregressive import init_model
 from .common import (EagerEma, SkipGuard, apply_trainable, averaged_weights, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
                      plot_predictions)
@@ -182,7 +183,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
           unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False, optimizer_kind: str = "adam",
           weight_decay: float = 0.0, init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100,
-          ema_decay: float = 0.0, ema_warmup: bool = False, ema_eval: bool = False):
+          ema_decay: float = 0.0, ema_warmup: bool = False, ema_eval: bool = False, objective: str = "nmse"):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     Fine-tuning: the model's ``requires_grad`` flags are honoured on every path (``common.apply_trainable``: --freeze / --train_only set
@@ -235,6 +236,13 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     bitwise.  ``ema_eval``: validation runs on the averaged weights (the trained ones are back afterwards), so ``dev_loss``, the plateau
     schedule, early stopping and the best checkpoint are the averaged model's.  Not with ``graph``: cfd_adam_multi has no such form.
 
+    ``objective`` = "rel_l2" | "nmse_sample" | "nmse_channel" (the FNO; "nmse": the loop as it always was): what the optimiser step
+    minimises (include/cfdbench_amd.h, "Training objectives").  ``fused``: FnoTrainEngine(objective=), on every route -- accumulation
+    groups, rollout windows, clipping, ``skip_nonfinite``, EMA, frozen subsets; eager: the model's loss becomes ``loss.ObjectiveLoss`` and
+    ``loss[objective].backward()`` replaces ``loss["nmse"].backward()``.  train_losses.json and ``dev_loss`` stay nmse, so runs remain
+    comparable; the objective's per-step values go to train_objective.json beside them (and ckpt-{ep}/train_objective.json), the log
+    line carries it under its name, train_state.pt carries both histories.  Not with ``graph`` or bf16 storage.
+
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
     other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop.
     ``gradient_accumulation_steps`` = N > 1 with ``fused``: FnoTrainEngine.accumulate per micro-batch (weight 1 / group) and
@@ -257,6 +265,19 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         raise NotImplementedError("--ema_decay needs --graph 0: cfd_adam_multi has no averaged form")
     if (ema_warmup or ema_eval) and not use_ema:
         raise ValueError("--ema_warmup / --ema_eval are options of --ema_decay D > 0")
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}")
+    obj = None if objective == "nmse" else objective
+    if obj is not None:
+        if not isinstance(model, Fno2d):
+            raise NotImplementedError("--objective other than nmse needs the fno model")
+        if graph:
+            raise NotImplementedError("--objective other than nmse needs --graph 0: the captured step backpropagates loss['nmse']")
+        if act_dtype not in ("fp32", "f32", "float32"):
+            raise NotImplementedError("--objective other than nmse needs --dtype fp32: bf16 storage runs the one-pass head")
+        if getattr(model.loss_fn, "objective", None) != obj:  # (evaluation then reports the objective beside the four scores)
+            model.loss_fn = objective_to_fn(obj)
+    key = obj or "nmse"  # the entry of the eager loss dict that is backpropagated
     unroll = int(unroll_steps)
     detach = bool(unroll_detach)
     if detach and unroll <= 1:
@@ -336,7 +357,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         # (adam: weight_decay stays unused, as in the reference)
         engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None,
                                 optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0,
-                                skip_nonfinite=guard.enabled, ema_decay=float(ema_decay) if use_ema else None, ema_warmup=bool(ema_warmup))
+                                skip_nonfinite=guard.enabled, ema_decay=float(ema_decay) if use_ema else None, ema_warmup=bool(ema_warmup),
+                                **(dict(objective=obj) if obj is not None else {}))
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -363,11 +385,16 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     global_step = 0
     grad_norm = None  # clipping: the last optimiser step's norm, on the device until the log line fetches it
     train_losses: List[float] = []
+    train_objective: List[float] = []  # (with an objective: its value per loss entry, beside train_losses)
     start_ep = 0
     state_path = output_dir / "train_state.pt"
     if resume and state_path.exists():
         state = torch.load(state_path, map_location="cpu", weights_only=False)
         check_resume_state(state, fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach))
+        if state.get("objective", "nmse") != objective:  # (a state without the key: written before the flag existed, i.e. nmse)
+            raise RuntimeError(f"train_state.pt was written with --objective {state.get('objective', 'nmse')}, this run uses "
+                               f"--objective {objective}: the two minimise different functions")
+        train_objective = list(state.get("train_objective", []))
         model.load_state_dict(torch.load(output_dir / state["ckpt"] / "model.pt", map_location="cpu"))
         if hasattr(model, "load_extra_train_state") and state.get("model_extra") is not None:
             model.load_extra_train_state(state["model_extra"])  # e.g. ResNet's dropout step counter
@@ -402,6 +429,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         ep_start_time = time.time()
         cur_lr = schedule.lr
         ep_train_losses: List = []
+        ep_train_obj: List = []  # (with an objective: one value per entry of ep_train_losses)
         ep_skipped: List = []  # fused --skip_nonfinite: per loss entry, whether its optimiser step was skipped (device booleans)
         logged = 0  # loss entries that earlier log lines of this epoch have averaged
         model.train()
@@ -431,6 +459,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                     ep_train_losses.append((wsums[:, 0] / wsums[:, 2]).mean())
                 else:
                     ep_train_losses.append((sums[0] / sums[2]).clone())
+                if obj is not None:  # (a device scalar; a window's (K,) values: their mean, like the nmse entry)
+                    ep_train_obj.append(engine.objective_value().mean().clone())
                 if guard.enabled and ((step + 1) % accum == 0 or step + 1 == n_steps):
                     # behind an optimiser call: its verdict (a device boolean, no sync) for every loss entry of its group
                     ep_skipped += [engine.last_step_skipped()] * (len(ep_train_losses) - len(ep_skipped))
@@ -462,10 +492,15 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             else:
                 if windows is not None:
                     nmse, preds_seq = unrolled_loss(model, batch["inputs"], batch["labels_seq"], batch["case_params"], batch["mask"],
-                                                    detach=detach)
+                                                    detach=detach, key=key)
                     with torch.no_grad():  # (the log line's mse: the last step's)
                         mse = ((preds_seq[-1] - batch["labels_seq"][-1] * batch["mask"]) ** 2).mean()
                     outputs = dict(preds=preds_seq[0], loss=dict(nmse=nmse, mse=mse))
+                    if obj is not None:  # (unrolled_loss summed the objective: the window's nmse for the history, without a graph)
+                        with torch.no_grad():
+                            labs = [l_ * batch["mask"] for l_ in batch["labels_seq"]]
+                            w_nmse = torch.stack([((p_ - l_) ** 2).sum() / (l_ ** 2).sum() for p_, l_ in zip(preds_seq, labs)]).mean()
+                        outputs["loss"] = {"nmse": w_nmse, "mse": mse, obj: nmse}
                 else:
                     outputs = model(**batch)
                 if step == 0 and not measure_time and rank == 0 and plot_interval > 0:
@@ -473,7 +508,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 loss = outputs["loss"]
                 # mean over the micro-batches of THIS group: the trailing group of an epoch may be shorter than `accum`
                 group = accum if step < n_full else n_steps - n_full
-                (loss["nmse"] / group if group > 1 else loss["nmse"]).backward()  # train_auto.py:255
+                (loss[key] / group if group > 1 else loss[key]).backward()  # train_auto.py:255
                 applied = True
                 if (step + 1) % accum == 0 or step + 1 == n_steps:
                     if world > 1:
@@ -489,8 +524,11 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                     optimizer.zero_grad()
                 if applied:
                     ep_train_losses.append(loss["nmse"].item())  # train_auto.py:260
+                    if obj is not None:
+                        ep_train_obj.append(loss[obj].item())
                 else:  # the loss history averages applied steps only: the skipped group's earlier micro-batches leave it
                     del ep_train_losses[len(ep_train_losses) - (step % accum):]
+                    del ep_train_obj[len(ep_train_obj) - (step % accum if obj is not None else 0):]
                 loss_mse, loss_nmse = loss["mse"], loss["nmse"]
             global_step += 1
             if guard.enabled and engine is not None and global_step % log_interval == 0:
@@ -506,6 +544,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 else:
                     mse_v, nmse_v = loss_mse.item(), loss_nmse.item()
                 line = dict(ep=ep, step=step, mse=f"{mse_v:.3e}", nmse=f"{nmse_v:.3e}", lr=f"{cur_lr:.3e}")
+                if obj is not None and ep_train_obj:  # (the last entry's: this batch's, a window's mean)
+                    line[obj] = f"{float(ep_train_obj[-1]):.3e}"
                 if clip:  # (fetched here only, where the loss has synchronised already)
                     gn = engine.grad_norm() if engine is not None else grad_norm
                     line["grad_norm"] = "nan" if gn is None else f"{float(gn):.3e}"
@@ -520,8 +560,12 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                 print(line)
         if engine is not None or graph:
             ep_train_losses = torch.stack(ep_train_losses).tolist() if ep_train_losses else []
+            if obj is not None:
+                ep_train_obj = torch.stack(ep_train_obj).tolist() if ep_train_obj else []
             if ep_skipped:  # (an epoch ends with its last group applied or skipped: one verdict per entry)
-                ep_train_losses = [v for v, s in zip(ep_train_losses, torch.stack(ep_skipped).tolist()) if not s]
+                verdicts = torch.stack(ep_skipped).tolist()
+                ep_train_losses = [v for v, s in zip(ep_train_losses, verdicts) if not s]
+                ep_train_obj = [v for v, s in zip(ep_train_obj, verdicts) if not s]
         if guard.enabled and engine is not None:
             guard.skipped = int(engine.skipped_steps())  # (behind the epoch's fetch: no sync of its own)
         schedule.epoch_end()
@@ -529,6 +573,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             print("Time usage:", time.time() - ep_start_time)
             return
         train_losses += ep_train_losses
+        train_objective += ep_train_obj
         if world > 1 and (ep + 1) % eval_interval == 0:
             average_buffers(model)  # BatchNorm running statistics of all shards go into the checkpoint
         result = None
@@ -543,6 +588,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             dev_scores = result["scores"]
             dump_json(dev_scores, ckpt_dir / "dev_scores.json")
             dump_json(ep_train_losses, ckpt_dir / "train_loss.json")
+            if obj is not None:
+                dump_json({obj: ep_train_obj}, ckpt_dir / "train_objective.json")
             ckpt_path = ckpt_dir / "model.pt"
             if ckpt_path.exists():
                 copyfile(ckpt_path, ckpt_dir / "backup_model.pt")
@@ -565,6 +612,7 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
                             rng=torch.get_rng_state(), fused=engine is not None, world=world, unroll_steps=unroll, unroll_detach=int(detach),
                             model_extra=model.extra_train_state() if hasattr(model, "extra_train_state") else None,
                             **(dict(skipped_steps=guard.skipped) if guard.enabled else {}),
+                            **(dict(objective=objective, train_objective=train_objective) if obj is not None else {}),
                             **(dict(eager_ema=ema.state_dict()) if use_ema and engine is None else {})), tmp)
             tmp.replace(state_path)
         else:
@@ -582,6 +630,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             break
     if rank == 0:
         dump_json(train_losses, output_dir / "train_losses.json")
+        if obj is not None:
+            dump_json({obj: train_objective}, output_dir / "train_objective.json")
         plot_loss(train_losses, output_dir / "train_losses.png")
     return train_losses
 
@@ -624,7 +674,7 @@ def main(argv=None):
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
               unroll_detach=bool(args.unroll_detach), optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
               init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips,
-              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval))
+              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval), objective=args.objective)
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         # (--ema_eval 1: the run chose its best checkpoint by the averaged weights' dev loss; the test runs on those weights)

@@ -113,7 +113,11 @@ class Fno2d(AutoCfdModel):
         preds, sums = F_.FnoForwardFn.apply(cfg, inputs, case_params, mask, label, *self.abi_parameters())
         if label is not None:
             normalize = bool(getattr(self.loss_fn, "normalize", True))
-            return dict(preds=preds, loss=F_.scores_from_sums(sums, normalize))
+            loss = F_.scores_from_sums(sums, normalize)
+            kind = getattr(self.loss_fn, "objective", None)  # (loss.ObjectiveLoss: one more autograd node on the predictions)
+            if kind is not None:
+                loss[kind] = F_.objective_loss(preds, label, kind, mask)
+            return dict(preds=preds, loss=loss)
         return dict(preds=preds)
 
     def get_coords(self, shape, device):  # fno2d.py:244-255 (kept for API compatibility; the kernels build coords in place)

@@ -28,9 +28,10 @@ def unroll_windows(dataset, K: int) -> Tuple[List[int], Tensor]:
 
 
 def unrolled_loss(model, inputs: Tensor, labels_seq: Sequence[Tensor], case_params: Tensor, mask: Optional[Tensor] = None,
-                  detach: bool = False):
+                  detach: bool = False, key: str = "nmse"):
     """``preds_1 = model(inputs)``, ``preds_k = model(preds_{k-1})``; returns ``(loss, preds)`` with ``loss = (1/K) sum_k nmse_k`` against
-    ``labels_seq[k - 1]`` and ``preds`` the K predictions.  ``loss.backward()`` reaches the parameters through every fed-back frame.
+    ``labels_seq[k - 1]`` and ``preds`` the K predictions.  ``key``: the entry of the model's loss dict to sum, e.g. "rel_l2" for a
+    model built with ``loss.objective_to_fn("rel_l2")``.  ``loss.backward()`` reaches the parameters through every fed-back frame.
 
     ``detach`` (the pushforward trick): the fed-back frame is ``preds.detach()`` -- step k + 1 trains on the model's own prediction as a
     constant input, so the gradient is the sum of K one-step gradients and nothing flows through the frames."""
@@ -45,7 +46,7 @@ def unrolled_loss(model, inputs: Tensor, labels_seq: Sequence[Tensor], case_para
         out = model(inputs=x, case_params=case_params, mask=mask, label=label)
         preds.append(out["preds"])
         x = out["preds"].detach() if detach else out["preds"]
-        loss = out["loss"]["nmse"] if loss is None else loss + out["loss"]["nmse"]
+        loss = out["loss"][key] if loss is None else loss + out["loss"][key]
     return loss / K, preds
 
 

@@ -722,6 +722,55 @@ int cfd_fno_backward_phase(const cfd_plan* plan, const cfd_fno_shape* shape, con
                            const float* mask, const float* label, const float* preds, const float* gpreds_ext,
                            const float* coef, void* ws, int phase, void* stream);
 
+/* Training objectives beside mse / nmse / mae (FnoTrainEngine(objective=...), functional.objective_loss): a value and its gradient with
+ * respect to the predictions, which enters the backward pass as gpreds_ext (cfd_fno_backward*, label = NULL, flags = 0).  No head kernel,
+ * no cfd_fno_* signature and no struct knows about them.
+ *
+ * preds, label: (B, Co, HW); mask: (B, HW) or NULL (= all ones).  d = preds - label * mask (preds already carries the mask, as
+ * cfd_fno_forward returns it), formed in fp32.  Per slice (b, c): E[b,c] = sum_p d^2, S[b,c] = sum_p (label * mask)^2, both accumulated
+ * in fp64; E_b = sum_c E[b,c], E_c = sum_b E[b,c], S_b and S_c likewise.
+ *   kind                      value                                   d value / d preds[b,c,p]
+ *   CFD_OBJ_REL_L2            (1/B)  sum_b sqrt(E_b) / sqrt(S_b)      d / (B sqrt(E_b) sqrt(S_b)); E_b == 0: 0 (torch's norm backward)
+ *   CFD_OBJ_NMSE_SAMPLE       (1/B)  sum_b E_b / S_b                  2 d / (B S_b)
+ *   CFD_OBJ_NMSE_CHANNEL      (1/Co) sum_c E_c / S_c                  2 d / (Co S_c)
+ * CFD_OBJ_REL_L2 is LpLoss(d=2, p=2).rel(preds, label * mask) of the reference's src/models/fno/utilities3.py:165-214.  S == 0 (an
+ * all-zero label slice) is not special-cased: the value and that group's gradient are inf / NaN, as in the reference.
+ *
+ * cfd_objective_fwd: TWO launches.  (1) k_obj_part: a workgroup owns one contiguous part of one slice -- NP = min(ceil(HW / 4096),
+ * CFD_OBJ_MAX_PARTS) parts per slice of ceil(HW / NP) elements rounded up to a multiple of 4, a function of (B, Co, HW) alone -- sums
+ * d^2 and (label * mask)^2 in fp64 per thread and then through LDS on a fixed tree, and stores one record.  (2) k_obj_final, one
+ * workgroup: the records of every group (a sample, or a channel), added in index order in fp64, give (E_g, S_g); value[0] is formed from
+ * them in fp64 and rounded once.  No atomics: two calls give the same bits.  16-byte loads where HW % 4 == 0 and preds, label and mask
+ * are 16-byte aligned; otherwise the scalar form, in which every thread owns the same elements in the same order: the same bits.
+ *
+ * rec: CFD_OBJ_REC_FLOATS(B, Co) floats on any 4-byte boundary, written by cfd_objective_fwd and read by cfd_objective_bwd with the same
+ * (B, Co, HW, kind); an fp64 is stored as two 32-bit words (low, high), as cfd_fno_params.clip stores its records:
+ *   rec[0..1]  the batch-global sum d^2               rec[2..3]  the batch-global sum (label * mask)^2          (fp64 each)
+ *   rec[4..5]  the value before its rounding (fp64)   rec[6..7]  not written
+ *   rec[8 + 4 g ..]       (E_g, S_g) of group g: g = b < B for the two per-sample kinds, g = c < Co for CFD_OBJ_NMSE_CHANNEL
+ *   rec[8 + 4 max(B, Co) + 4 r ..]   (E, S) of part record r = (b Co + c) NP + part
+ * The rest of the buffer is not written.  rec[0..3] let a caller log the batch-global nMSE (rec[0..1] / rec[2..3]) without another pass.
+ *
+ * cfd_objective_bwd: ONE launch (three for fwd + bwd), elementwise on the same split.  Every workgroup reads the two fp64 sums of its
+ * slice's group -- finalised once by k_obj_final, so no workgroup re-adds part records -- forms
+ *   coef = upstream * (upstream_dev ? upstream_dev[0] : 1) * {1 / (B sqrt(E_g) sqrt(S_g)), 2 / (B S_g), 2 / (Co S_g)}       in fp64
+ * and writes gpreds = (gadd ? gadd : 0) + fp32(coef * d): the product in fp64, rounded once, then one fp32 addition when gadd is given.
+ * gpreds may alias gadd (each element is read and written by one thread).  upstream_dev: one device float, e.g. the upstream gradient of
+ * an autograd node, read without a host synchronisation.
+ *
+ * Alignment: every tensor and rec on any 4-byte boundary.  Refusals before any launch, nothing written: unknown kind, B / Co / HW < 1,
+ * NULL preds / label / rec / value / gpreds: CFD_ERR_INVALID_ARG.                                                                        */
+#define CFD_OBJ_REL_L2 0
+#define CFD_OBJ_NMSE_SAMPLE 1
+#define CFD_OBJ_NMSE_CHANNEL 2
+#define CFD_OBJ_MAX_PARTS 8
+#define CFD_OBJ_REC_FLOATS(B, Co) \
+    (8 + 4 * (size_t)((B) > (Co) ? (B) : (Co)) + 4 * (size_t)(B) * (size_t)(Co) * CFD_OBJ_MAX_PARTS)
+int cfd_objective_fwd(const float* preds, const float* label, const float* mask, float* rec, float* value, int B, int Co, int HW,
+                      int kind, void* stream);
+int cfd_objective_bwd(const float* preds, const float* label, const float* mask, const float* rec, const float* gadd,
+                      const float* upstream_dev, float upstream, float* gpreds, int B, int Co, int HW, int kind, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
