@@ -32,6 +32,11 @@ def CFD_OBJ_REC_FLOATS(B: int, Co: int) -> int:
     return 8 + 4 * max(int(B), int(Co)) + 4 * int(B) * int(Co) * CFD_OBJ_MAX_PARTS
 
 
+def CFD_HS_REC_FLOATS(B: int, Co: int) -> int:
+    """Floats of the `rec` buffer of cfd_sobolev_fwd / _bwd ("Sobolev objective"): the header's macro of the same name."""
+    return 2 + 12 * int(B) + 12 * int(B) * int(Co)
+
+
 class CfdError(RuntimeError):
     pass
 
@@ -199,6 +204,8 @@ _SIGS = {
                               _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "cfd_objective_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfd_objective_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
+    "cfd_sobolev_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "cfd_sobolev_bwd": (_I, [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
 }
 
 

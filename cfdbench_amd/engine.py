@@ -30,8 +30,9 @@ from torch import Tensor
 
 from . import _lib
 from ._capi import (CFD_CLIP_CONSECUTIVE, CFD_CLIP_FLOATS, CFD_CLIP_SKIPPED, CFD_STEP_ACCUM_INIT, CFD_STEP_ACCUMULATE, CFD_STEP_DECOUPLED_WD,
-                    CFD_STEP_SKIP_NONFINITE, CFD_OBJ_REC_FLOATS, OBJECTIVE_IDS)
+                    CFD_STEP_SKIP_NONFINITE, CFD_HS_REC_FLOATS, CFD_OBJ_REC_FLOATS, OBJECTIVE_IDS)
 from .functional import _param_struct
+from .sobolev import HS_NAME, hs_arguments
 
 _LOSS_IDS = {"mse": 0, "nmse": 1, "mae": 2}
 _ACT_DTYPES = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -352,7 +353,8 @@ class FnoTrainEngine:
                  weight_decay: float = 0.0, loss_name: str = "nmse", group=None, grad_buckets: int = 1,
                  overlap: bool = True, fused_head: bool = True, act_dtype: str = "fp32", max_grad_norm: Optional[float] = None,
                  trainable: Optional[Sequence[str]] = None, optimizer: str = "adam", skip_nonfinite: bool = False,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = False, objective: Optional[str] = None):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False, objective: Optional[str] = None,
+                 hs_k: Optional[int] = None, hs_a: Optional[Sequence[float]] = None, hs_group: Optional[bool] = None):
         """``trainable``: state_dict key prefixes (``{"fc1", "fc2"}``, ``{"blocks.3", "fc1", "fc2"}``) of the parameters to train; the
         others are frozen (their ``requires_grad`` is set to match).  None: the engine honours ``requires_grad`` as it finds it.  The
         flat buffers (parameters, gradient, moments, accumulator, what a data-parallel run exchanges) hold the trainable tensors only, and
@@ -404,6 +406,10 @@ class FnoTrainEngine:
         do.  Nothing is deferred and the one-pass head is not used: ``loss_name`` must stay "nmse" and bf16 activation storage is
         refused (ValueError).  Data-parallel runs exchange once behind the pass, each rank's objective over its own batch.
         ``objective_value()`` is the device scalar of the last pass ((K,) for a window).
+        ``objective`` = "hs": the relative Sobolev norm (include/cfdbench_amd.h, "Sobolev objective": HsLoss of the reference's FNO
+        directory) with ``hs_k`` (1 or 2; default 1), ``hs_a`` (the k weights; default ones) and ``hs_group`` (the balanced form; default
+        False).  The pass is the same call for call, with cfd_sobolev_fwd / cfd_sobolev_bwd on the predictions' data grid (H, W) -- also
+        under domain padding -- in place of cfd_objective_fwd / _bwd.  The ``hs_*`` arguments with another objective: ValueError.
 
         ``act_dtype`` = "bf16": bf16-storage training (src/args.py:77-80 of the fork's other trainers): the saved
         activations a_0 .. a_L are rounded to bf16 when stored -- half the bytes of what the backward pass re-reads -- and the
@@ -417,13 +423,16 @@ class FnoTrainEngine:
         if self.act_dtype and not fused_head:
             raise ValueError("bf16 activation storage runs the one-pass training head: fused_head must be True")
         if objective is not None:
-            if objective not in OBJECTIVE_IDS:
-                raise ValueError(f"objective must be None or one of {sorted(OBJECTIVE_IDS)}")
+            if objective not in OBJECTIVE_IDS and objective != HS_NAME:
+                raise ValueError(f"objective must be None or one of {sorted(OBJECTIVE_IDS) + [HS_NAME]}")
             if loss_name != "nmse":
                 raise ValueError("an objective replaces the loss the step minimises; the reported loss stays nmse: loss_name must be 'nmse'")
             if self.act_dtype:
                 raise ValueError("an objective runs the two-pass head: bf16 activation storage (the one-pass head) is not available")
+        if objective != HS_NAME and not (hs_k is None and hs_a is None and hs_group is None):
+            raise ValueError(f"hs_k, hs_a and hs_group are arguments of objective={HS_NAME!r}")
         self.objective = objective
+        self.hs = hs_arguments(1 if hs_k is None else hs_k, hs_a, bool(hs_group)) if objective == HS_NAME else None
         if optimizer not in ("adam", "adamw"):
             raise ValueError("optimizer must be 'adam' or 'adamw'")
         self.optimizer = optimizer
@@ -517,7 +526,8 @@ class FnoTrainEngine:
         self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
         self.preds = torch.empty((B, c["out_chan"], H, W), dtype=torch.float32, device=self.device)
         if self.objective is not None:  # (per shape, like preds: a captured graph replays on these addresses)
-            self._obj_rec = torch.empty(CFD_OBJ_REC_FLOATS(B, c["out_chan"]), dtype=torch.float32, device=self.device)
+            floats = CFD_HS_REC_FLOATS if self.hs is not None else CFD_OBJ_REC_FLOATS
+            self._obj_rec = torch.empty(floats(B, c["out_chan"]), dtype=torch.float32, device=self.device)
             self._obj_gpreds = torch.empty_like(self.preds)
             self._obj_value = torch.zeros((), dtype=torch.float32, device=self.device)
             self._obj_last = self._obj_value
@@ -532,9 +542,15 @@ class FnoTrainEngine:
         a = self.api
         inputs, cp, mk, label, preds = data
         B, Co, HW = self.shape.B, self.shape.out_chan, self.shape.H * self.shape.W
-        kind, rec, gp = OBJECTIVE_IDS[self.objective], self._obj_rec.data_ptr(), self._obj_gpreds.data_ptr()
-        a.call("cfd_objective_fwd", preds, label, mk, rec, value.data_ptr(), B, Co, HW, kind, st)
-        a.call("cfd_objective_bwd", preds, label, mk, rec, gadd, None, float(upstream), gp, B, Co, HW, kind, st)
+        rec, gp = self._obj_rec.data_ptr(), self._obj_gpreds.data_ptr()
+        if self.hs is not None:  # (the predictions' data grid: a padded model still returns (B, Co, H, W))
+            H, W = self.shape.H, self.shape.W
+            a.call("cfd_sobolev_fwd", preds, label, mk, rec, value.data_ptr(), B, Co, H, W, *self.hs, st)
+            a.call("cfd_sobolev_bwd", preds, label, mk, rec, gadd, None, float(upstream), gp, B, Co, H, W, *self.hs, st)
+        else:
+            kind = OBJECTIVE_IDS[self.objective]
+            a.call("cfd_objective_fwd", preds, label, mk, rec, value.data_ptr(), B, Co, HW, kind, st)
+            a.call("cfd_objective_bwd", preds, label, mk, rec, gadd, None, float(upstream), gp, B, Co, HW, kind, st)
         for phase in range(last_phase + 1):
             a.call("cfd_fno_backward_phase_f", plan, sh, pr, gr, inputs, cp, mk, None, preds, gp, None, sums, ws, phase, _LOSS_IDS["mse"], 0,
                    0, st)

@@ -48,7 +48,10 @@ the same attribute table drives ``argparse``.  Differences, all documented in SU
     ``objective`` (train_auto, the fno model: what the step MINIMISES -- nmse = the reference's loop, unchanged | rel_l2 = the per-sample
     relative L2 norm, LpLoss(d=2, p=2).rel of the reference's src/models/fno/utilities3.py | nmse_sample | nmse_channel; --fused 1:
     FnoTrainEngine(objective=), eager: ``loss.ObjectiveLoss``; the loss history and the log line carry its value beside nmse, dev_loss
-    and the checkpoint choice stay on nmse; not with --graph 1 or --dtype bf16).
+    and the checkpoint choice stay on nmse; not with --graph 1 or --dtype bf16; hs = the relative Sobolev norm, HsLoss of the same
+    file: FnoTrainEngine(objective="hs") / ``loss.SobolevLoss``),
+    ``hs_k`` (1 | 2: the highest derivative order of --objective hs), ``hs_a`` (A1[,A2]: the weights of the orders, "" = ones),
+    ``hs_group`` (1: HsLoss's balanced form, every order's relative norm on its own).
 Flags of models that are not built yet are carried so existing command lines and args.json files keep working.
 """
 from __future__ import annotations
@@ -81,10 +84,24 @@ _FLAGS: Dict[str, Any] = dict(
     lr_scheduler="step", early_stop=0, gradient_accumulation_steps=1, unroll_steps=1, max_grad_norm=0.0,
     fused_accumulation_steps=1, unroll_detach=0, freeze="", train_only="", optimizer="adam", init_from="",
     skip_nonfinite=0, max_consecutive_skips=100, ema_decay=0.0, ema_warmup=0, ema_eval=0, objective="nmse",
+    hs_k=1, hs_a="", hs_group=0,
     # Fno2d(padding=): the reference's constructor argument (fno2d.py:139) that its init_model never passes; None = no domain padding
     fno_padding=None,
 )
 OBJECTIVES = ("nmse", "rel_l2", "nmse_sample", "nmse_channel")  # --objective: nmse = today's loop
+ALL_OBJECTIVES = OBJECTIVES + ("hs",)  # ... and the Sobolev objective with its --hs_* flags
+
+
+def parse_hs_a(text: str):
+    """--hs_a "A1[,A2]" -> (A1[, A2]); "" -> None (ones)."""
+    return tuple(float(x) for x in str(text).split(",")) if str(text).strip() else None
+
+
+def hs_arguments_of(args) -> dict:
+    """The (k, a, group) of --objective hs as keyword arguments of ``loss.SobolevLoss``; {} for every other objective."""
+    if getattr(args, "objective", "nmse") != "hs":
+        return {}
+    return dict(k=int(args.hs_k), a=parse_hs_a(args.hs_a), group=bool(args.hs_group))
 _OPTIONAL_INT = ("fno_padding",)  # flags whose default is None: parsed as int when given
 
 
@@ -171,7 +188,17 @@ def is_args_valid(args: Args) -> None:
         assert not args.ema_warmup and not args.ema_eval, "--ema_warmup / --ema_eval are options of --ema_decay D > 0"
     if args.graph:
         assert not args.ema_decay > 0.0, "--graph 1 with --ema_decay is not built: cfd_adam_multi has no averaged form"
-    assert args.objective in OBJECTIVES, f"--objective is one of {', '.join(OBJECTIVES)}"
+    assert args.objective in ALL_OBJECTIVES, f"--objective is one of {', '.join(ALL_OBJECTIVES)}"
+    if args.objective == "hs":
+        assert args.hs_k in (1, 2), "--hs_k is 1 or 2"
+        assert args.hs_group in (0, 1), "--hs_group is 0 or 1"
+        try:
+            hs_a = parse_hs_a(args.hs_a)
+        except ValueError:
+            raise AssertionError("--hs_a is A1 or A1,A2: numbers separated by a comma") from None
+        assert hs_a is None or len(hs_a) == args.hs_k, "--hs_a gives one weight per order: --hs_k numbers"
+    else:
+        assert args.hs_k == 1 and args.hs_a == "" and args.hs_group == 0, "--hs_k / --hs_a / --hs_group are options of --objective hs"
     if args.objective != "nmse":
         assert args.model == "fno", "--objective other than nmse is built for the fno model (its gradient enters Fno2d's backward pass)"
         assert not args.graph, "--graph 1 with an --objective is not built: the captured step backpropagates loss['nmse']"

@@ -35,6 +35,8 @@ def get_output_dir(args, is_auto: bool = False) -> Path:
             name += f"_pad{args.fno_padding}"
         if getattr(args, "objective", "nmse") != "nmse":  # (likewise: a run on another objective gets a directory of its own)
             name += f"_obj-{args.objective}"
+            if args.objective == "hs":  # (_obj-hs-k{k}[-a...][-grp])
+                name += f"-k{args.hs_k}" + (f"-a{args.hs_a}" if args.hs_a else "") + ("-grp" if args.hs_group else "")
     elif m == "resnet":
         name = f"lr{args.lr}_d{args.resnet_depth}_w{args.resnet_hidden_chan}"
     elif m == "auto_edeeponet":

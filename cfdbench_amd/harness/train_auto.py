@@ -33,7 +33,7 @@ from ..models.base_model import AutoCfdModel
 from ..models.fno.fno2d import Fno2d
 from ..unroll import collate_windows, unroll_windows, unrolled_loss
 from ..models.loss import objective_to_fn
-from .args import OBJECTIVES, Args, is_args_valid
+from .args import ALL_OBJECTIVES, Args, hs_arguments_of, is_args_valid
 from .autoregressive import init_model
 from .common import (EagerEma, SkipGuard, apply_trainable, averaged_weights, dump_json, get_output_dir, load_best_ckpt, load_ckpt, make_optimizer, plot, plot_loss,
                      plot_predictions)
@@ -183,7 +183,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
           early_stopping_delta: float = 1e-5, gradient_accumulation_steps: int = 1, act_dtype: str = "fp32", graph: bool = False,
           unroll_steps: int = 1, max_grad_norm: float = 0.0, unroll_detach: bool = False, optimizer_kind: str = "adam",
           weight_decay: float = 0.0, init_from: str = "", skip_nonfinite: bool = False, max_consecutive_skips: int = 100,
-          ema_decay: float = 0.0, ema_warmup: bool = False, ema_eval: bool = False, objective: str = "nmse"):
+          ema_decay: float = 0.0, ema_warmup: bool = False, ema_eval: bool = False, objective: str = "nmse",
+          hs_k: Optional[int] = None, hs_a=None, hs_group: Optional[bool] = None):
     """train_auto.py:181-313.  ``fused`` selects FnoTrainEngine (needs an Fno2d and the nmse loss).
 
     Fine-tuning: the model's ``requires_grad`` flags are honoured on every path (``common.apply_trainable``: --freeze / --train_only set
@@ -242,6 +243,9 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
     ``loss[objective].backward()`` replaces ``loss["nmse"].backward()``.  train_losses.json and ``dev_loss`` stay nmse, so runs remain
     comparable; the objective's per-step values go to train_objective.json beside them (and ckpt-{ep}/train_objective.json), the log
     line carries it under its name, train_state.pt carries both histories.  Not with ``graph`` or bf16 storage.
+    ``objective`` = "hs": the relative Sobolev norm ("Sobolev objective" there) with ``hs_k`` (1 | 2), ``hs_a`` (the k weights, None: ones)
+    and ``hs_group``; ``fused``: FnoTrainEngine(objective="hs", hs_k=, hs_a=, hs_group=), eager: ``loss.SobolevLoss``.  The three
+    arguments with another objective: ValueError.
 
     ``lr_scheduler_kind`` / ``early_stopping_patience`` / ``gradient_accumulation_steps``: the training options of this fork's
     other trainers (harness/schedule.py; src/args.py:53-56,77-80,323) -- the defaults are the reference's benchmark loop.
@@ -265,9 +269,16 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         raise NotImplementedError("--ema_decay needs --graph 0: cfd_adam_multi has no averaged form")
     if (ema_warmup or ema_eval) and not use_ema:
         raise ValueError("--ema_warmup / --ema_eval are options of --ema_decay D > 0")
-    if objective not in OBJECTIVES:
-        raise ValueError(f"objective must be one of {OBJECTIVES}")
+    if objective not in ALL_OBJECTIVES:
+        raise ValueError(f"objective must be one of {ALL_OBJECTIVES}")
     obj = None if objective == "nmse" else objective
+    hs = {}
+    if obj == "hs":
+        from ..sobolev import hs_arguments
+        hs = dict(k=1 if hs_k is None else hs_k, a=None if hs_a is None else tuple(hs_a), group=bool(hs_group))
+        hs_arguments(**hs)  # (ValueError on what the kernels refuse)
+    elif not (hs_k is None and hs_a is None and hs_group is None):
+        raise ValueError("hs_k, hs_a and hs_group are arguments of objective='hs'")
     if obj is not None:
         if not isinstance(model, Fno2d):
             raise NotImplementedError("--objective other than nmse needs the fno model")
@@ -275,8 +286,10 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
             raise NotImplementedError("--objective other than nmse needs --graph 0: the captured step backpropagates loss['nmse']")
         if act_dtype not in ("fp32", "f32", "float32"):
             raise NotImplementedError("--objective other than nmse needs --dtype fp32: bf16 storage runs the one-pass head")
-        if getattr(model.loss_fn, "objective", None) != obj:  # (evaluation then reports the objective beside the four scores)
-            model.loss_fn = objective_to_fn(obj)
+        # (evaluation then reports the objective beside the four scores)
+        if getattr(model.loss_fn, "objective", None) != obj or (hs and (model.loss_fn.hs_k, model.loss_fn.hs_a, model.loss_fn.hs_group)
+                                                                != (hs["k"], hs["a"], hs["group"])):
+            model.loss_fn = objective_to_fn(obj, **hs)
     key = obj or "nmse"  # the entry of the eager loss dict that is backpropagated
     unroll = int(unroll_steps)
     detach = bool(unroll_detach)
@@ -358,7 +371,8 @@ def train(model: AutoCfdModel, train_data, dev_data, output_dir: Path, num_epoch
         engine = FnoTrainEngine(model, lr=lr, loss_name="nmse", act_dtype=act_dtype, max_grad_norm=float(max_grad_norm) if clip else None,
                                 optimizer=optimizer_kind, weight_decay=float(weight_decay) if optimizer_kind == "adamw" else 0.0,
                                 skip_nonfinite=guard.enabled, ema_decay=float(ema_decay) if use_ema else None, ema_warmup=bool(ema_warmup),
-                                **(dict(objective=obj) if obj is not None else {}))
+                                **(dict(objective=obj) if obj is not None else {}),
+                                **({"hs_" + k_: v_ for k_, v_ in hs.items()} if hs else {}))
         optimizer = None
     elif graph:
         if accum > 1 or getattr(model, "graph_unsafe", False):
@@ -674,7 +688,8 @@ def main(argv=None):
               act_dtype=args.dtype, graph=bool(args.graph), unroll_steps=args.unroll_steps, max_grad_norm=args.max_grad_norm,
               unroll_detach=bool(args.unroll_detach), optimizer_kind=args.optimizer, weight_decay=args.weight_decay,
               init_from=args.init_from, skip_nonfinite=bool(args.skip_nonfinite), max_consecutive_skips=args.max_consecutive_skips,
-              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval), objective=args.objective)
+              ema_decay=args.ema_decay, ema_warmup=bool(args.ema_warmup), ema_eval=bool(args.ema_eval), objective=args.objective,
+              **{"hs_" + k_: v_ for k_, v_ in hs_arguments_of(args).items()})
     if "test" in args.mode and rank == 0:  # the test split is small: rank 0 evaluates it alone
         args.save(str(output_dir / "test_args.json"))
         # (--ema_eval 1: the run chose its best checkpoint by the averaged weights' dev loss; the test runs on those weights)

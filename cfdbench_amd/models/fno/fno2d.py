@@ -114,9 +114,9 @@ class Fno2d(AutoCfdModel):
         if label is not None:
             normalize = bool(getattr(self.loss_fn, "normalize", True))
             loss = F_.scores_from_sums(sums, normalize)
-            kind = getattr(self.loss_fn, "objective", None)  # (loss.ObjectiveLoss: one more autograd node on the predictions)
+            kind = getattr(self.loss_fn, "objective", None)  # (loss.ObjectiveLoss / SobolevLoss: one more autograd node on the predictions)
             if kind is not None:
-                loss[kind] = F_.objective_loss(preds, label, kind, mask)
+                loss[kind] = self.loss_fn.objective_value(preds, label, mask)
             return dict(preds=preds, loss=loss)
         return dict(preds=preds)
 

@@ -6,7 +6,7 @@ from typing import List
 from torch import Tensor, nn
 
 from .._capi import OBJECTIVE_IDS
-from ..functional import mse_loss_scores, objective_loss
+from ..functional import mse_loss_scores, objective_loss, sobolev_loss
 
 
 class MseLoss(nn.Module):
@@ -39,15 +39,38 @@ class ObjectiveLoss(MseLoss):
     def get_score_names(self) -> List[str]:
         return super().get_score_names() + [self.objective]
 
+    def objective_value(self, preds: Tensor, labels: Tensor, mask=None) -> Tensor:
+        return objective_loss(preds, labels, self.objective, mask)
+
     def forward(self, preds: Tensor, labels: Tensor) -> dict:
         out = super().forward(preds, labels)
-        out[self.objective] = objective_loss(preds, labels, self.objective)
+        out[self.objective] = self.objective_value(preds, labels)
         return out
 
 
-def objective_to_fn(name: str) -> MseLoss:
-    """"nmse" (``loss_name_to_fn``'s) or an objective's name; anything else raises like ``loss_name_to_fn``."""
+class SobolevLoss(ObjectiveLoss):
+    """The four scores of ``MseLoss(normalize=True)`` plus "hs", the relative Sobolev norm HsLoss(d=2, p=2, k, a, group) of the reference's
+    src/models/fno/utilities3.py (``functional.sobolev_loss``), listed last."""
+
+    def __init__(self, k: int = 1, a=None, group: bool = False):
+        from ..sobolev import HS_NAME, hs_arguments
+        hs_arguments(k, a, group)  # (raises on what the kernels refuse)
+        MseLoss.__init__(self, normalize=True)
+        self.objective = HS_NAME
+        self.hs_k, self.hs_a, self.hs_group = int(k), (None if a is None else tuple(float(x) for x in a)), bool(group)
+
+    def objective_value(self, preds: Tensor, labels: Tensor, mask=None) -> Tensor:
+        return sobolev_loss(preds, labels, mask, self.hs_k, self.hs_a, self.hs_group)
+
+
+def objective_to_fn(name: str, **hs) -> MseLoss:
+    """"nmse" (``loss_name_to_fn``'s), an objective's name, or "hs" with ``SobolevLoss``'s arguments (k, a, group); anything else raises
+    like ``loss_name_to_fn``."""
     name = name.lower()
+    if name == "hs":
+        return SobolevLoss(**hs)
+    if hs:
+        raise ValueError(f"k, a and group are arguments of the objective 'hs', not of {name!r}")
     return ObjectiveLoss(name) if name in OBJECTIVE_IDS else loss_name_to_fn(name)
 
 

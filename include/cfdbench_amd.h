@@ -771,6 +771,56 @@ int cfd_objective_fwd(const float* preds, const float* label, const float* mask,
 int cfd_objective_bwd(const float* preds, const float* label, const float* mask, const float* rec, const float* gadd,
                       const float* upstream_dev, float upstream, float* gpreds, int B, int Co, int HW, int kind, void* stream);
 
+/* Sobolev objective (FnoTrainEngine(objective="hs"), functional.sobolev_loss): the relative H^s norm of HsLoss in the reference's
+ * src/models/fno/utilities3.py, a value and its gradient with respect to the predictions, which enters the backward pass as gpreds_ext
+ * exactly as the training objectives above do.
+ *
+ * preds, label: (B, Co, H, W) fp32; mask: (B, H, W) or NULL (= all ones).  lm = label * mask, rounded on its own; d = preds - lm, one
+ * fp32 rounding (both as above).  Wave numbers, the reference's rule as it stands: kx(i) = i if i < H / 2 (integer division) else H - i,
+ * ky(j) likewise with W -- for an odd size this is not symmetric under i -> H - i (H = 5: 0 1 3 2 1) -- and r(i, j) = kx(i)^2 + ky(j)^2.
+ * With Dh = fft2(d), Yh = fft2(lm) over (H, W), unnormalised, per sample b (over its Co channels and all H W modes), t = 0, 1, 2:
+ *   E_t[b] = sum r^t |Dh|^2,   S_t[b] = sum r^t |Yh|^2          (fp64)
+ * and A_0 = 1, A_1 = a1^2, A_2 = a2^2 (a2 is not read at k = 1):
+ *   balanced 0   value = (1/B) sum_b sqrt(E[b]) / sqrt(S[b]),  E[b] = sum_{t<=k} A_t E_t[b],  S[b] likewise;
+ *                d value / d preds[b, c] = Re F^H (q_b Dh[b, c]),  q_b(i, j) = (sum_{t<=k} A_t r^t) / (B sqrt(E[b]) sqrt(S[b]))
+ *   balanced 1   value = (1 / (B (k+1))) sum_b sum_{t<=k} sqrt(A_t E_t[b]) / sqrt(A_t S_t[b])      (a_t = 0 gives 0/0 = NaN: the reference's)
+ *                q_b(i, j) = sum_{t<=k} r^t / (B (k+1) sqrt(E_t[b]) sqrt(S_t[b]))
+ * F^H is the unnormalised inverse transform (H W ifft2).  A term whose E is exactly 0 has coefficient 0 (CFD_OBJ_REL_L2's rule); S == 0
+ * is not special-cased: the value and that sample's gradient are inf / NaN.  With a1 = 0, k = 1, balanced 0 this is CFD_OBJ_REL_L2: by
+ * Parseval E_0 = H W sum d^2, and the factor cancels.
+ *
+ * Kernels (csrc/sobolev.hip): one workgroup per (b, c) image; the half spectrum (columns l <= W / 2) by two real GEMM stages on
+ * v_mfma_f32_16x16x4_f32 -- stage W against [cos | -sin], stage H complex against the H x H table; per element the instruction's fp32
+ * accumulator takes segments of eight terms in k order from zero, the segments are added in fp64 and the element is rounded once (a
+ * single fp32 chain of up to 256 terms costs the head's bias gradient, a cancelling sum over all pixels, its tolerance) -- with twiddles from a 1-D table of N entries per axis that every workgroup forms in LDS ((i k) mod N in integers, sin / cos
+ * in double, one rounding).  Element (i, l) of the half spectrum carries the weight of itself and, unless l == 0 or 2 l == W, of its
+ * mirror image (-i, W - l): the same sums and the same gradient as the full spectrum.  The spectrum stays in LDS.
+ *
+ * cfd_sobolev_fwd: TWO launches.  k_hs_fwd leaves the record (E_0, E_1, E_2, S_0, S_1, S_2) of every image: fp64, per lane in tile
+ * order, then a fixed tree; k_hs_final, one workgroup, adds a sample's records in channel order and forms the value in fp64, rounded
+ * once into value[0].  No atomics: two calls give the same bits.
+ * rec: CFD_HS_REC_FLOATS(B, Co) floats on any 4-byte boundary, an fp64 stored as two 32-bit words (low, high):
+ *   rec[0..1]                     the value before its rounding
+ *   rec[2 + 12 b + 2 t ..]        E_t[b], t = 0, 1, 2;   rec[2 + 12 b + 6 + 2 t ..]  S_t[b]
+ *   rec[2 + 12 B + 12 (b Co + c) ..]   the record of image (b, c), in the same order
+ *
+ * cfd_sobolev_bwd: ONE launch.  Recomputes d and its spectrum, multiplies by the weight polynomial in fp64 (rounded to fp32), runs the
+ * two stages backwards and writes gpreds = (gadd ? gadd : 0) + fp32(c * x): c = upstream * (upstream_dev ? upstream_dev[0] : 1) /
+ * (B sqrt(E) sqrt(S)) (balanced: / (B (k+1) sqrt(E_0) sqrt(S_0)), the other terms' ratios inside the polynomial) in fp64, one rounding of
+ * the term, then one fp32 addition when gadd is given.  gpreds may alias gadd.  It takes the (B, Co, H, W, k, a1, a2, balanced) of the
+ * cfd_sobolev_fwd call that wrote rec.
+ *
+ * Range: 2 <= H, W <= 128, B, Co >= 1, B Co < 2^31; LDS by the shape, at most 160 KB (128 x 128: 152 KB, one workgroup per CU).
+ * Alignment: every tensor and rec on any 4-byte boundary; 16-byte loads where W % 4 == 0 and preds, label, mask are 16-byte aligned,
+ * the scalar form otherwise, with the same bits.  Refusals before any launch, nothing written: k outside {1, 2}, balanced outside
+ * {0, 1}, B / Co < 1, NULL preds / label / rec / value / gpreds: CFD_ERR_INVALID_ARG; a grid outside the range: CFD_ERR_UNSUPPORTED.    */
+#define CFD_HS_REC_FLOATS(B, Co) (2 + 12 * (size_t)(B) + 12 * (size_t)(B) * (size_t)(Co))
+int cfd_sobolev_fwd(const float* preds, const float* label, const float* mask, float* rec, float* value, int B, int Co, int H, int W,
+                    int k, float a1, float a2, int balanced, void* stream);
+int cfd_sobolev_bwd(const float* preds, const float* label, const float* mask, const float* rec, const float* gadd,
+                    const float* upstream_dev, float upstream, float* gpreds, int B, int Co, int H, int W, int k, float a1, float a2,
+                    int balanced, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
